@@ -20,11 +20,15 @@ batch each (`--lanes`, captra_amd.graph.TrackLanes: every lane replays its own c
 over to itself; the frame's poses reach the exchange through a ring of records).  A step still passes every trajectory of the rank
 through one frame, and the timed region ends with a device-wide synchronize + barrier.
 
-Prints ONE JSON line on rank 0 (see the keys below).  `roofline` describes the dominant kernel
-family of the step, measured with HIP events on the launch stream over the same steps launched eagerly right after the
-timed region, networks one after the other (a launch's duration is then the kernel's own);
-`cpu_baseline` is the CPU oracle (oracle/, a port of the reference's CPU path) timed on the host
-cores of rank 0 at N=1 on a bounded sample of the same workload at batch 1.
+Prints ONE JSON line on rank 0 (see the keys below).  A plain run sets up, warms up, times ONE block of exactly --steps
+steps and prints the headline (`value`, `ms_per_step`); `--dump-outputs DIR` writes the poses the last timed step handed
+back as DIR/pose_<key>.npy (float32; inputs and weights are seeded, so the same arguments give the same inputs).
+Everything else is measured with `--full` only: repeated timed blocks (>= 10 s of GPU work, value from the median block),
+`roofline` -- the dominant kernel family of the step, measured with HIP events on the launch stream over the same steps
+launched eagerly right after the timed region, networks one after the other (a launch's duration is then the kernel's own)
+--, the ball-query / group op figures, the CPU-oracle check of the last step (`pose_match`), the `otf` / `b1` / `legs`
+processes, live counter passes, and `cpu_baseline`: the CPU oracle (oracle/, a port of the reference's CPU path) timed on
+the host cores of rank 0 at N=1 on a bounded sample of the same workload at batch 1.
 """
 from __future__ import annotations
 
@@ -624,6 +628,14 @@ def pose_match(cfg, sd, frame_cpu, prev_pose, new_pose, which=(0, 1)):
             "agree_5deg5cm": float(hit), "within_1e-4": bool(max(float((ref[k] - ours[k]).abs().max()) for k in ref) <= 1e-4)}
 
 
+def dump_outputs(out_dir: str, pose: dict) -> None:
+    """What the timed path handed its caller in its last step -- the (B, P, ...) pose dict of this rank's trajectories -- as
+    one float32 .npy per key (a few KB at any batch this bench runs)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in pose.items():
+        np.save(os.path.join(out_dir, f"pose_{k}.npy"), v.detach().to(torch.float32).cpu().numpy())
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as s:
@@ -675,11 +687,19 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=20, help="untimed steps before the timed region; at least 20 are run whatever the flag (SURVEY.md 8d)")
     ap.add_argument("--min-warmup", type=int, default=20, help=argparse.SUPPRESS)   # profiling recipes only (short traces)
-    ap.add_argument("--repeats", type=int, default=10,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed block of exactly --steps steps (barrier + synchronize on both sides) is run this many times back to "
-                         "back; `value` / `ms_per_step` come from the MEDIAN block, min / max are reported beside it")
-    ap.add_argument("--min-timed-s", type=float, default=10.0,
-                    help="keep running timed blocks (beyond --repeats) until they add up to this many seconds of GPU work")
+                         "back; `value` / `ms_per_step` come from the MEDIAN block, min / max are reported beside it (default: 1; "
+                         "10 with --full)")
+    ap.add_argument("--min-timed-s", type=float, default=None,
+                    help="keep running timed blocks (beyond --repeats) until they add up to this many seconds of GPU work (default: 0; "
+                         "10 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline: repeated timed blocks, per-kernel timing and rooflines, the "
+                         "CPU-oracle check of the last step, the otf / b1 / legs processes, live counter passes, the CPU baseline "
+                         "(each can still be switched off with its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the poses the last timed step returned as DIR/pose_<key>.npy (float32)")
     ap.add_argument("--batch", type=int, default=32, help="trajectories per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket kernels with HIP events")
@@ -719,6 +739,14 @@ def main():
     if args.dry_run:
         print(json.dumps(launch_plan(args.gpus)))
         return
+    args.full = args.full or args.leg              # a leg is one configuration of a --full run
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_pose_match = args.no_otf = args.no_b1 = args.no_legs = True
+        args.no_live_traffic = True
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 1
+    if args.min_timed_s is None:
+        args.min_timed_s = 10.0 if args.full else 0.0
     if args.leg:
         args.no_cpu_baseline = args.no_otf = args.no_b1 = args.no_legs = True
         args.no_pose_match = args.mlp_dtype != "f32x6"          # (the f32x6 leg carries its own pose_match: the mode's claim is accuracy + speed)
@@ -850,21 +878,24 @@ def main():
         if eager_timing and r == 0:
             _lib.prof_enable(False)
             fused.WORK["on"] = False
-    # the last step once more, keeping its input and output pose, for pose_match (outside every timed block)
-    if lanes is not None:
-        prev_pose = {k: v.clone() for k, v in pose.items()}
-        last_pose = {k: v.clone() for k, v in step(done, pose).items()}
-    else:
-        prev_pose = {k: v.clone() for k, v in pose.items()}
-        last_pose = {k: v.clone() for k, v in step(done, prev_pose).items()}
-    last_frame = frame_of(done)
-    torch.cuda.synchronize()
-    # the level-1 stream kernel's own stamps of the step just replayed (100 MHz counter): where the sampler ended inside the launch
-    l1_spans = None
-    if getattr(model, "_l1_scratch", None) is not None:
-        model.check_l1_stream()
-        sp = fused.sa1_stream_spans(model._l1_scratch)
-        l1_spans = {"sampler_us": round(sp[0], 1), "launch_us": round(sp[1], 1)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pose)     # (sync() has run: the last step's poses are complete)
+    last_pose, l1_spans = pose, None
+    if args.full:
+        # the last step once more, keeping its input and output pose, for pose_match (outside every timed block)
+        if lanes is not None:
+            prev_pose = {k: v.clone() for k, v in pose.items()}
+            last_pose = {k: v.clone() for k, v in step(done, pose).items()}
+        else:
+            prev_pose = {k: v.clone() for k, v in pose.items()}
+            last_pose = {k: v.clone() for k, v in step(done, prev_pose).items()}
+        last_frame = frame_of(done)
+        torch.cuda.synchronize()
+        # the level-1 stream kernel's own stamps of the step just replayed (100 MHz counter): where the sampler ended inside the launch
+        if getattr(model, "_l1_scratch", None) is not None:
+            model.check_l1_stream()
+            sp = fused.sa1_stream_spans(model._l1_scratch)
+            l1_spans = {"sampler_us": round(sp[0], 1), "launch_us": round(sp[1], 1)}
     timed_steps = args.steps
     if timing and not eager_timing:
         # the timed blocks replayed a hipGraph; the per-kernel HIP events come from the same steps

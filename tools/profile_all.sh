@@ -9,7 +9,7 @@ tools/profile_round.sh $TAG
 tools/profile_round.sh $TAG _bf16 --mlp-dtype bf16
 tools/profile_round.sh $TAG _drawers --category drawers
 tools/profile_backbone.sh $TAG
-python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 python bench.py --leg --mlp-dtype bf16 > $OUT/${TAG}_bench_bf16.json 2> $OUT/${TAG}_bench_bf16.err
 python bench.py --leg --category drawers > $OUT/${TAG}_bench_drawers.json 2> $OUT/${TAG}_bench_drawers.err
 python tools/bench_backbone.py --npoint 2048 512 > $OUT/${TAG}_backbone16k.json 2> $OUT/${TAG}_backbone16k.err

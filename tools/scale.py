@@ -30,10 +30,10 @@ def plan(max_gpus: int = 8, steps: int = 20, warmup: int = 20) -> list[dict]:
     n = 1
     while n <= max_gpus:
         runs.append({"name": f"configs[1] bottle fp32 x{n}", "gpus": n,
-                     "cmd": [sys.executable, BENCH, "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup)] + (legs if n > 1 else ["--no-legs"])})
+                     "cmd": [sys.executable, BENCH, "--full", "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup)] + (legs if n > 1 else ["--no-legs"])})
         n *= 2
     runs.append({"name": f"configs[2] mix6 bf16 x{max_gpus}", "gpus": max_gpus,
-                 "cmd": [sys.executable, BENCH, "--gpus", str(max_gpus), "--steps", str(steps), "--warmup", str(warmup), "--category", "mix6",
+                 "cmd": [sys.executable, BENCH, "--full", "--gpus", str(max_gpus), "--steps", str(steps), "--warmup", str(warmup), "--category", "mix6",
                          "--mlp-dtype", "bf16"] + legs})
     runs.append({"name": f"configs[4] backbone16k x{max_gpus}", "gpus": max_gpus,
                  "cmd": [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={max_gpus}", "--master-addr", "127.0.0.1",
