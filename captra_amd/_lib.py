@@ -103,6 +103,8 @@ _SIGNATURES = {
     "captra_row_max": [_LL, _INT, _P, _P, _P],
     "captra_pack_pose": [_INT, _P, _P, _P, _P, _P, _P, _P],
     "captra_procrustes_rot3": [_INT, _INT, _P, _P, _P, _P],
+    "captra_box_iou": [_INT, _INT, _INT, _INT, _P, _P, _P, _P, _P],
+    "captra_part_extent": [_INT, _INT, _INT, _P, _P, _P, _P],
 }
 
 

@@ -3,6 +3,8 @@ misc/eval/eval.py:27-111).  For every frame after the first of every `<experimen
 (written by `captra_amd.track --save`, layout of model.py:482-509): rotation / translation / scale errors and the
 5 deg 5 cm / 10 deg 10 cm flags per part (part_dof_utils.py:54-67), box IoUs (pose_utils/bbox_utils.py), and for
 articulated objects the joint-state error; writes results/err.pkl + results/err.csv and prints the averages.
+`--eval_device` computes the box IoUs on the GPU, all frames of a pickle in one call (same columns; grid IoUs agree with the
+host protocol within the grid's resolution).
 """
 from __future__ import annotations
 
@@ -15,7 +17,7 @@ import numpy as np
 import torch
 
 from .configs.config import get_config
-from .pose_utils.bbox_utils import eval_instance_part_iou
+from .pose_utils.bbox_utils import eval_instance_part_iou, eval_single_part_iou_device
 from .pose_utils.metrics import rot_diff_degree
 from .pose_utils.part_dof_utils import eval_part_full
 
@@ -36,18 +38,34 @@ def get_joint_state(info: dict, pose: dict) -> np.ndarray:
     return np.array(states)
 
 
-def eval_data(name: str, data: dict, obj_info: dict) -> dict:
+def device_ious(data: dict, sym: bool, rigid: bool, device) -> np.ndarray:
+    """`--eval_device`: the 'iou' entry of eval_instance_part_iou for every frame after the first of one result pickle, on the GPU
+    in one call (pose_utils/bbox_utils.py eval_single_part_iou_device) -> (T-1, P) float64."""
+    frames = range(1, len(data["pred"]["poses"]))
+    stack = lambda poses: {k: torch.as_tensor(np.stack([np.asarray(poses[i][k], np.float32) for i in frames])).unsqueeze(1).to(device)
+                           for k in ("rotation", "translation", "scale")}
+    pred_corners = torch.as_tensor(np.stack([np.asarray(data["pred"]["corners"][i], np.float32) for i in frames])).unsqueeze(1).to(device)
+    gt_corners = torch.as_tensor(np.asarray(data["gt"]["corners"], np.float32)).unsqueeze(0).to(device)
+    res = eval_single_part_iou_device(gt_corners, pred_corners, stack(data["gt"]["poses"]), stack(data["pred"]["poses"]), nocs=rigid, sym=sym)
+    return res["iou"][:, 0].double().cpu().numpy()
+
+
+def eval_data(name: str, data: dict, obj_info: dict, device=None) -> dict:
     sym, rigid = obj_info["sym"], obj_info["num_parts"] == 1
     gt_corners = np.asarray(data["gt"]["corners"])
     errors = {}
+    ious = device_ious(data, sym, rigid, device) if device is not None and len(data["pred"]["poses"]) > 1 else None
     for i in range(1, len(data["pred"]["poses"])):          # frame 0 is the initialisation
         gt = {k: torch.as_tensor(np.asarray(v)) for k, v in data["gt"]["poses"][i].items()}
         pred = {k: torch.as_tensor(np.asarray(v)) for k, v in data["pred"]["poses"][i].items()}
         _, per = eval_part_full(gt, pred, per_instance=True, yaxis_only=sym)
         row = {k: float(np.asarray(v)) for k, v in per.items()}
-        iou = eval_instance_part_iou(gt_corners, np.asarray(data["pred"]["corners"][i]), {k: v.numpy() for k, v in gt.items()},
-                                   {k: v.numpy() for k, v in pred.items()}, nocs=rigid, sym=sym)
-        row.update({f"iou_{j}": float(v) for j, v in enumerate(iou["iou"])})
+        if ious is not None:
+            row.update({f"iou_{j}": float(v) for j, v in enumerate(ious[i - 1])})
+        else:
+            iou = eval_instance_part_iou(gt_corners, np.asarray(data["pred"]["corners"][i]), {k: v.numpy() for k, v in gt.items()},
+                                         {k: v.numpy() for k, v in pred.items()}, nocs=rigid, sym=sym)
+            row.update({f"iou_{j}": float(v) for j, v in enumerate(iou["iou"])})
         if not rigid:
             diff = np.abs(get_joint_state(obj_info, {k: v.numpy() for k, v in pred.items()})
                           - get_joint_state(obj_info, {k: v.numpy() for k, v in gt.items()}))
@@ -70,12 +88,21 @@ def main(argv=None) -> dict:
     ap.add_argument("--obj_config", type=str, default=None)
     ap.add_argument("--obj_category", type=str, default=None)
     ap.add_argument("--experiment_dir", type=str, default=None)
-    cfg = get_config(ap.parse_args(argv), save=False)
+    ap.add_argument("--eval_device", action="store_true", default=False,
+                    help="box IoUs on the GPU, all frames of a pickle in one call (opt-in; default the host numpy protocol)")
+    args = ap.parse_args(argv)
+    device = None
+    if args.eval_device:
+        if not torch.cuda.is_available():
+            raise SystemExit("--eval_device needs a GPU (there is no fall-back: drop the flag for the host protocol)")
+        device = torch.device("cuda", torch.cuda.current_device())
+    del args.eval_device
+    cfg = get_config(args, save=False)
     data_path = pjoin(cfg["experiment_dir"], "results", "data")
     errors = {}
     for raw in sorted(os.listdir(data_path)):
         with open(pjoin(data_path, raw), "rb") as f:
-            errors.update(eval_data(raw.rsplit(".", 1)[0], pickle.load(f), cfg["obj_info"]))
+            errors.update(eval_data(raw.rsplit(".", 1)[0], pickle.load(f), cfg["obj_info"], device))
     if not errors:
         raise SystemExit(f"no result pickles under {data_path}")
     err_path = pjoin(cfg["experiment_dir"], "results", "err.pkl")

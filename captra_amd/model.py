@@ -129,6 +129,10 @@ class EvalTrackModel(BaseModel):
         # replay one captured hipGraph per frame instead of launching the ~140 kernels of a step one by one
         # (captra_amd/graph.py); opt-in: `--hipgraph` of captra_amd.track / cfg['hipgraph'].  Same kernels, same bits.
         self.use_graph = bool(cfg.get("hipgraph", False))
+        # Box IoUs and predicted NOCS corners of the evaluation on the GPU (captra_amd/csrc/box_iou.hip) instead of the host numpy
+        # protocol; opt-in: `--eval_device` of captra_amd.track / cfg['eval_device'].  IoUs agree within the grid's resolution
+        # (DESIGN.md), corners bit for bit.
+        self.eval_device = bool(cfg.get("eval_device", False))
         # arithmetic of the shared MLPs for THIS model (None = whatever the calling thread has set, default exact fp32);
         # "bf16" = BASELINE.json configs[2].  Entered around every step (fused.use_mlp_dtype): no process-wide switch.
         self.mlp_dtype = cfg.get("mlp_dtype")
@@ -670,14 +674,21 @@ class EvalTrackModel(BaseModel):
         coordinates: per part the symmetric extent [-max|x|, +max|x|] (model.py:489-493) -- the same boxes compute_loss
         evaluates, so the offline IoU tables (captra_amd/eval.py) agree with the in-loop avg_iou."""
         from .loss import choose_coord_by_label
-        from .pose_utils.bbox_utils import get_pred_nocs_corners
+        from .pose_utils.bbox_utils import get_pred_nocs_corners, pred_nocs_corners_device
         gt_corners = self.feed_dict[0]["meta"]["nocs_corners"].cpu().numpy()
-        corner_list = [None]
+        corner_list, maps = [None], []
         for i in range(1, len(self.pred_dict["poses"])):
             pred = self.pred_dict["npcs_pred"][i]
             pred_labels = torch.max(pred["seg"], dim=-2)[1]                                        # (B,N)
             pred_nocs = choose_coord_by_label(pred["nocs"].transpose(-1, -2), pred_labels)         # (B,N,3)
-            corner_list.append(get_pred_nocs_corners(pred_labels, pred_nocs, self.num_parts))
+            if self.eval_device:
+                maps.append((pred_labels, pred_nocs))
+            else:
+                corner_list.append(get_pred_nocs_corners(pred_labels, pred_nocs, self.num_parts))
+        if maps:
+            # every frame in one launch and one read; float64 at the pickle boundary like the host function (same values, bit for bit)
+            corners = pred_nocs_corners_device(torch.stack([m[0] for m in maps]), torch.stack([m[1] for m in maps]), self.num_parts)
+            corner_list.extend(corners.double().cpu().numpy())
         to_np = lambda pose: {k: v.detach().cpu().numpy() for k, v in pose.items()}
         save_dict = {"pred": {"poses": [to_np(p) for p in self.pred_dict["poses"]], "corners": corner_list},
                      "gt": {"poses": [to_np(f["gt_part"]) for f in self.feed_dict], "corners": gt_corners},
@@ -696,7 +707,7 @@ class EvalTrackModel(BaseModel):
         1..T-1 for the prediction and for its initialisation (= the previous frame's prediction), the segmentation and
         NOCS losses of CoordinateNet's maps when the frames carry labels / NOCS, and with `eval_iou` the three box IoUs
         (canonical boxes, posed predicted box, ground-truth box under the predicted pose; host-side numpy as in the
-        reference).  Keys as in the reference, including its quirk of storing the per-frame NOCS losses under
+        reference, or with cfg['eval_device'] all frames in one call on the GPU: `_device_iou`).  Keys as in the reference, including its quirk of storing the per-frame NOCS losses under
         'frame_seg'."""
         from .loss import choose_coord_by_label, compute_miou_loss, compute_nocs_loss
         from .pose_utils.bbox_utils import eval_single_part_iou, get_pred_nocs_corners
@@ -704,6 +715,7 @@ class EvalTrackModel(BaseModel):
         avg_iou, all_iou, seg_losses, all_seg, nocs_losses, all_nocs = {}, {}, [], {}, [], {}
         poses = self.pred_dict["poses"]
         gt_corners = self.feed_dict[0]["meta"]["nocs_corners"].float().cpu()                       # (B,P,2,3)
+        device_frames = []              # eval_device: (frame, predicted labels, own-part NOCS) of the frames whose IoUs are still to come
         for i, pose in enumerate(poses):
             diff, per = eval_part_full(self.feed_dict[i]["gt_part"], pose, per_instance=per_instance, yaxis_only=self.sym)
             all_pred[i] = deepcopy(diff)
@@ -726,7 +738,9 @@ class EvalTrackModel(BaseModel):
                 all_nocs[i] = compute_nocs_loss(npcs_pred["nocs"], npcs_feed["nocs"], labels=pred_labels, confidence=None,
                                                 loss="l2", self_supervise=False, per_instance=False)
                 nocs_losses.append(all_nocs[i])
-            if eval_iou:
+            if eval_iou and self.eval_device:
+                device_frames.append((i, pred_labels, choose_coord_by_label(npcs_pred["nocs"].transpose(-1, -2), pred_labels)))
+            elif eval_iou:
                 pred_nocs = choose_coord_by_label(npcs_pred["nocs"].transpose(-1, -2), pred_labels)                 # (B,N,3)
                 pred_corners = torch.from_numpy(get_pred_nocs_corners(pred_labels, pred_nocs, self.num_parts)).float()
                 iou, per_iou = eval_single_part_iou(gt_corners, pred_corners, self.feed_dict[i]["gt_part"], pose,
@@ -736,6 +750,8 @@ class EvalTrackModel(BaseModel):
                 if per_instance:
                     self.record_per_diff(self.feed_dict[i], per_iou)
                 all_iou[i] = deepcopy(iou)
+        if device_frames:
+            self._device_iou(device_frames, gt_corners, per_instance, avg_iou, all_iou)
         n = max(len(poses) - 1, 1)
         loss_dict = {"avg_pred": divide_dict(avg_pred, n), "avg_init": divide_dict(avg_init, n),
                      "frame_pred": all_pred, "frame_init": all_init}
@@ -746,6 +762,26 @@ class EvalTrackModel(BaseModel):
         if eval_iou:
             loss_dict.update({"avg_iou": divide_dict(avg_iou, n), "frame_iou": all_iou})
         self.loss_dict = loss_dict
+
+    def _device_iou(self, frames, gt_corners, per_instance, avg_iou, all_iou):
+        """cfg['eval_device']: the box IoUs of all `frames` on the GPU (pose_utils/bbox_utils.py, captra_box_iou /
+        captra_part_extent) -- one corner launch, one IoU call, one read -- then the same entries as the host path: batch means as
+        Python floats into `avg_iou` / `all_iou`, per-instance float64 arrays into the per-instance records."""
+        from .pose_utils.bbox_utils import eval_single_part_iou_device, pred_nocs_corners_device
+        names, idx = ("npcs_iou", "iou", "gt_bbox_iou"), [f[0] for f in frames]
+        pred_corners = pred_nocs_corners_device(torch.stack([f[1] for f in frames]), torch.stack([f[2] for f in frames]), self.num_parts)
+        dev = pred_corners.device
+        stack = lambda ds: {k: torch.stack([d[k].to(dev) for d in ds]) for k in ("rotation", "translation", "scale")}
+        res = eval_single_part_iou_device(gt_corners.to(dev), pred_corners, stack([self.feed_dict[i]["gt_part"] for i in idx]),
+                                          stack([self.pred_dict["poses"][i] for i in idx]), nocs=self.nocs_otf, sym=self.sym)
+        host = torch.stack([res[name] for name in names]).double().cpu().numpy()                   # (3,F,B,P): the only read
+        for f, i in enumerate(idx):
+            per_iou = {name: {p: host[k, f, :, p].copy() for p in range(host.shape[-1])} for k, name in enumerate(names)}
+            iou = {name: {p: float(np.mean(v)) for p, v in d.items()} for name, d in per_iou.items()}
+            add_dict(avg_iou, iou)
+            if per_instance:
+                self.record_per_diff(self.feed_dict[i], per_iou)
+            all_iou[i] = deepcopy(iou)
 
     def test(self, save=False, no_eval=False, epoch=0):
         self.forward(save=save)

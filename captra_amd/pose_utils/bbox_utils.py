@@ -5,6 +5,10 @@ box corners are ordered i -> (x = (i % 4) // 2, y = i // 4, z = i % 2) picking m
 (NOCS) categories score the axis-aligned extent of the posed corners (`nocs_iou_3d`, l.45-61); articulated parts
 score oriented boxes by occupancy on a 50^3 grid spanning both boxes (`iou_3d`, l.28-42); symmetric objects take
 the best of 20 rotations of the ground truth about its y axis (l.164-176).
+
+The numpy functions are the pinned restatement of the reference and the default.  Their device counterparts at the end of the
+file (`box_iou_device`, `pred_nocs_corners_device`, `eval_single_part_iou_device`; cfg['eval_device']) run the same protocol on
+the GPU for a whole trajectory per launch (captra_amd/csrc/box_iou.hip).
 """
 from __future__ import annotations
 
@@ -162,3 +166,83 @@ def eval_single_part_iou(gt_corners, pred_corners, gt_pose: dict, pred_pose: dic
     per = {name: {p: np.array([r[name][p] for r in rows]) for p in range(gc.shape[1])} for name in ("npcs_iou", "iou", "gt_bbox_iou")}
     mean = {name: {p: np.mean(v) for p, v in d.items()} for name, d in per.items()}
     return mean if separate is True else per if separate is False else (mean, per)
+
+
+# ---- device counterparts (captra_amd/csrc/box_iou.hip; opt-in: cfg['eval_device']) ---------------------------------------------------
+# Same protocol, evaluated by captra_box_iou / captra_part_extent on the GPU, a whole trajectory per launch; the numpy functions
+# above stay the pinned restatement of the reference.  Results are device tensors: the caller reads them once.
+_Y_ROTATIONS = {}
+
+
+def box_iou_device(gt_boxes, pred_boxes, nocs: bool, nres: int = 50, return_counts: bool = False):
+    """Best IoU of every predicted box against its candidate ground-truth boxes: gt_boxes (J,C,8,3), pred_boxes (J,8,3) fp32 device
+    tensors -> (J,) fp32 (`part_iou` for J boxes at once: nocs_iou_3d when `nocs`, else iou_3d on an nres^3 grid); with
+    `return_counts` also the (J,C,2) int32 intersection / union counts of the occupancy form (None for `nocs`)."""
+    import torch
+    from .. import _lib as L
+    gt = gt_boxes.contiguous().float()
+    pred = pred_boxes.contiguous().float()
+    L.require_device(gt, pred)
+    J, C = gt.shape[0], gt.shape[1]
+    if gt.shape != (J, C, 8, 3) or pred.shape != (J, 8, 3):
+        raise ValueError(f"box_iou_device: gt_boxes {tuple(gt.shape)} / pred_boxes {tuple(pred.shape)}: expected (J,C,8,3) / (J,8,3)")
+    iou = torch.empty(J, dtype=torch.float32, device=gt.device)
+    counts = None if nocs else torch.empty(J, C, 2, dtype=torch.int32, device=gt.device)
+    with torch.cuda.device(gt.device):
+        L.call("captra_box_iou", J, C, 1 if nocs else 0, nres, L.ptr(pred), L.ptr(gt), L.ptr(iou), L.ptr(counts))
+    return (iou, counts) if return_counts else iou
+
+
+def pred_nocs_corners_device(pred_seg, nocs_pred, num_parts: int):
+    """`get_pred_nocs_corners` on the device: labels (...,N), the points' own-part NOCS (...,N,3) -> (...,P,2,3) fp32 device tensor,
+    the same values bit for bit (a maximum of absolute values does not depend on the order)."""
+    import torch
+    from .. import _lib as L
+    lab = pred_seg.to(torch.int32).contiguous()
+    nocs = nocs_pred.float().contiguous()
+    L.require_device(lab, nocs)
+    if nocs.shape != lab.shape + (3,):
+        raise ValueError(f"pred_nocs_corners_device: labels {tuple(lab.shape)} / nocs {tuple(nocs.shape)}")
+    lead, n = lab.shape[:-1], lab.shape[-1]
+    out = torch.empty(lead + (num_parts, 2, 3), dtype=torch.float32, device=lab.device)
+    with torch.cuda.device(lab.device):
+        L.call("captra_part_extent", out.numel() // (num_parts * 6), num_parts, n, L.ptr(lab), L.ptr(nocs), L.ptr(out))
+    return out
+
+
+def _pose_box_device(pose: dict, box):
+    """`pose_box` on device tensors: rotation (...,3,3), translation (...,3,1), scale (...) ; box (...,8,3)."""
+    posed = (box.unsqueeze(-2) * pose["rotation"].unsqueeze(-3)).sum(-1) * pose["scale"][..., None, None]
+    return posed + pose["translation"].transpose(-1, -2)
+
+
+def eval_single_part_iou_device(gt_corners, pred_corners, gt_pose: dict, pred_pose: dict, nocs: bool = False, sym: bool = False) -> dict:
+    """The three box IoUs of `eval_single_part_iou` on the device: corners (...,B,P,2,3), poses of (...,B,P,...) device tensors, with
+    any leading (frame) axes -- `gt_corners` may come without them -- -> {'npcs_iou', 'iou', 'gt_bbox_iou'}: (...,B,P) fp32 device
+    tensors.  Posing and the 20 rotations of a symmetric object's ground truth are torch on the device; the IoUs are one
+    captra_box_iou call for all three."""
+    import torch
+    dev = pred_corners.device
+    f32 = lambda d: {k: v.to(dev).float() for k, v in d.items()}
+    gt_pose, pred_pose = f32(gt_pose), f32(pred_pose)
+    pred_box = tensor_bbox_from_corners(pred_corners.float())
+    gt_box = tensor_bbox_from_corners(gt_corners.to(dev).float()).expand(pred_box.shape)
+    lead = pred_box.shape[:-2]
+    if sym:
+        if dev not in _Y_ROTATIONS:
+            _Y_ROTATIONS[dev] = torch.from_numpy(np.stack([_y_rotation(2 * np.pi * i / 20) for i in range(20)])).to(dev)
+        rot = (gt_pose["rotation"][..., None, :, :, None] * _Y_ROTATIONS[dev][:, None, :, :]).sum(-2)    # R Y_c: (...,20,3,3)
+        cand = {"rotation": rot, "translation": gt_pose["translation"].unsqueeze(-3).expand(rot.shape[:-1] + (1,)),
+                "scale": gt_pose["scale"].unsqueeze(-1).expand(rot.shape[:-2])}
+        gt_posed = _pose_box_device(cand, gt_box.unsqueeze(-3))                                   # (...,C,8,3)
+    else:
+        gt_posed = _pose_box_device(gt_pose, gt_box).unsqueeze(-3)
+    C = gt_posed.shape[-3]
+    flat = lambda x: x.reshape((-1,) + x.shape[len(lead):])
+    canon_gt, canon_pred = flat(gt_box.unsqueeze(-3)), flat(pred_box)
+    posed_gt = flat(gt_posed)
+    posed_pred = [flat(_pose_box_device(pred_pose, pred_box)), flat(_pose_box_device(pred_pose, gt_box))]
+    # one call: the canonical pair takes its single candidate C times over (the best of equal values is that value)
+    out = box_iou_device(torch.cat([canon_gt.expand(-1, C, -1, -1), posed_gt, posed_gt]), torch.cat([canon_pred] + posed_pred), nocs)
+    npcs, iou, gtb = out.reshape((3,) + tuple(lead))
+    return {"npcs_iou": npcs, "iou": iou, "gt_bbox_iou": gtb}

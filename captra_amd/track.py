@@ -4,7 +4,8 @@ Builds the config from the same flags (`a/b` names override cfg['a']['b'], parse
 resumes the RotationNet experiment and the CoordNet experiment (`--coord_exp/dir`), walks the trajectories and
 prints, per trajectory and overall, the reference's two throughput lines -- with a device synchronisation before
 each clock read, which the reference lacks -- then the averaged pose errors; `--save` writes the per-trajectory
-result pickles of model.py:482-509.
+result pickles of model.py:482-509.  `--eval_device` moves the evaluation's box IoUs and predicted NOCS corners to the GPU
+(cfg['eval_device'], opt-in).
 
 Data: `--data DIR` reads pre-cropped trajectories (`captra_amd/trajectory_io.py`: one .npz per trajectory);
 `--data synthetic[:nocs|:arti]` generates the seeded S-nocs / S-arti trajectories of SURVEY.md §8d (needs this
@@ -56,6 +57,8 @@ def parse_args(argv=None):
                         help="bf16: bf16 MFMA operands / fp32 accumulation in the shared MLPs (opt-in; default exact fp32)")
     parser.add_argument("--hipgraph", action="store_true", default=False,
                         help="replay one captured hipGraph per frame (same kernels, no per-launch host overhead)")
+    parser.add_argument("--eval_device", action="store_true", default=False,
+                        help="box IoUs and predicted NOCS corners of the evaluation on the GPU (opt-in; default the host numpy protocol)")
     return parser.parse_args(argv)
 
 
@@ -204,11 +207,12 @@ def iter_batches(args, cfg, ranks: Ranks | None = None):
 
 def main(argv=None) -> dict:
     args = parse_args(argv)
-    data_args = {k: getattr(args, k) for k in ("data", "num_traj", "num_frames", "random_init", "seed", "hipgraph", "mlp_dtype")}
+    data_args = {k: getattr(args, k) for k in ("data", "num_traj", "num_frames", "random_init", "seed", "hipgraph", "mlp_dtype", "eval_device")}
     for k in data_args:
         delattr(args, k)
     cfg = get_config(args, save=False)
     cfg["hipgraph"] = data_args["hipgraph"]
+    cfg["eval_device"] = data_args["eval_device"]
     cfg["mlp_dtype"] = data_args["mlp_dtype"]          # per-model setting (EvalTrackModel.mlp_dtype), no process-wide switch
     args = argparse.Namespace(**vars(args), **data_args)
     ranks = Ranks()

@@ -665,6 +665,24 @@ typedef struct captra_sa_scale_job {
 } captra_sa_scale_job;
 int captra_sa_scales_multi(int njobs, const captra_sa_scale_job *jobs, const captra_launch_opts *opts, captra_stream_t stream);
 
+/* Box IoUs of the evaluation tables (pose_utils/bbox_utils.py:11-61: pts_inside_box, iou_3d, nocs_iou_3d; the best of the candidate
+ * ground-truth boxes as in calc_part_iou_list, l.128-158).  pred_box (njobs,8,3) and gt_box (njobs,ncand,8,3) are corner points in
+ * the order of bbox_from_corners -> iou (njobs) = the best IoU of a job's box against its candidates, the first one on ties.
+ *   mode 0, occupancy: per (job, candidate) an nres^3 grid (2 <= nres <= 128) over the joint extent of the 16 corners; a point is
+ *     inside a box iff 0 < (p - c4).u < u.u for u = c5 - c4, c7 - c4, c0 - c4; IoU = inter / union in fp32, 1 when no grid point is
+ *     inside either box.  Grid coordinates are the float32 values of numpy.linspace(lo, hi, nres): step = fl(fl(hi - lo) / (nres - 1)),
+ *     coordinate i = fl(fl(i * step) + lo), the last one hi, all lo when hi == lo.  counts (njobs,ncand,2) i32 is REQUIRED: the
+ *     launcher zeroes it and leaves the intersection and union counts there (integer sums: the same on every run).
+ *   mode 1, axis-aligned extents: min / max over the 8 corners of each box, intersection 0 when any overlap edge is negative, volumes
+ *     as (x * y) * z in fp32, IoU = inter / (v1 + v2 - inter); nres and counts are ignored (counts may be NULL). */
+int captra_box_iou(int njobs, int ncand, int mode, int nres, const float *pred_box, const float *gt_box, float *iou, int *counts,
+                   captra_stream_t stream);
+
+/* Predicted NOCS corners (get_pred_nocs_corners, bbox_utils.py:107-125): labels (B,N) i32, nocs (B,N,3) -> out (B,P,2,3) =
+ * [-max|x|, +max|x|] per axis over the points of a cloud that carry the part's label, zeros for a part without points; labels
+ * outside [0, p) are ignored; p <= 64.  A maximum of absolute values: exact in any order. */
+int captra_part_extent(int b, int p, int n, const int *labels, const float *nocs, float *out, captra_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Section 3 — introspection
  * ---------------------------------------------------------------------------------------- */
