@@ -22,7 +22,7 @@ _lib = None
 
 _INT, _LL, _F, _P = C.c_int, C.c_longlong, C.c_float, C.c_void_p
 
-# name -> argtypes (all return int unless listed in _VOID / _OTHER)
+# launchers: name -> argtypes (all return int; the last argument is the stream)
 _SIGNATURES = {
     "captra_furthest_point_sampling": [_INT, _INT, _INT, _P, _P, _P, _P],
     "captra_ball_query": [_INT, _INT, _INT, _F, _INT, _P, _P, _P, _P],
@@ -105,6 +105,51 @@ _SIGNATURES = {
     "captra_procrustes_rot3": [_INT, _INT, _P, _P, _P, _P],
     "captra_box_iou": [_INT, _INT, _INT, _INT, _P, _P, _P, _P, _P],
     "captra_part_extent": [_INT, _INT, _INT, _P, _P, _P, _P],
+}
+
+# auxiliary entry points (sizes, tile counts, knobs, profiling): name -> (argtypes, restype)
+_AUX_SIGNATURES = {
+    "captra_error_string": ([_INT], C.c_char_p),
+    "captra_version": ([], C.c_char_p),
+    "captra_prof_enable": ([_INT], None),
+    "captra_prof_reset": ([], None),
+    "captra_prof_read": ([C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)], _INT),
+    "captra_prof_names": ([C.c_char_p, _INT], _INT),
+    "captra_group_points_grad_ws_bytes": ([_INT] * 5, C.c_size_t),
+    "captra_three_interpolate_grad_ws_bytes": ([_INT] * 4, C.c_size_t),
+    "captra_gather_points_grad_ws_bytes": ([_INT] * 4, C.c_size_t),
+    "captra_packed_weight_floats": ([_INT, _INT], _LL),
+    "captra_dense_bf16_image_bytes": ([_INT, _INT], _LL),
+    "captra_gn_stats_bf16pm_tiles": ([_LL], _INT),
+    "captra_dense_bf16_stats_tiles": ([_LL], _INT),
+    "captra_dense_bf16_tile_stats_tiles": ([_LL], _INT),
+    "captra_chain_bf16_image_bytes": ([_INT, _INT], _LL),
+    "captra_dense_x6_image_bytes": ([_INT, _INT], _LL),
+    "captra_sa_x6_image_bytes": ([_INT] * 4, _LL),
+    "captra_sa_bf16_image_bytes": ([_INT] * 4, _LL),
+    "captra_sa1_stream_scratch_bytes": ([_INT, _INT], _LL),
+    "captra_sa1_stream_set_grid": ([_INT, _INT], None),
+    "captra_sa1_stream_set_fine": ([_INT], None),
+    "captra_sa1_stream_set_whole": ([_INT], None),
+    "captra_neck_chain_set_split": ([_INT], None),
+    "captra_query_and_group_set_shape": ([_INT, _INT], None),
+    "captra_pointwise_mlp_gn_tiles": ([_INT, _INT, _LL], _INT),
+    "captra_pointwise_mlp_gn_tiles_ex": ([_INT, _INT, _LL, _P], _INT),
+}
+
+# A/B switches for measurements: environment variable -> (thread-local knob of the library, arguments after the variable's integer);
+# set once, for the thread that loads the library
+_ENV_SWITCHES = {
+    "CAPTRA_BF16_SHARED_AFFINE": ("captra_dense_bf16_set_shared_affine", ()),
+    "CAPTRA_SA_BF16_VARIANT": ("captra_sa_bf16_set_variant", ()),
+    "CAPTRA_FPS_DEFER": ("captra_fps_set_defer", ()),
+    "CAPTRA_NN_SPLIT": ("captra_three_nn_set_split", ()),
+    "CAPTRA_BQ_CPW": ("captra_ball_query_set_cpw", ()),
+    "CAPTRA_SA_SPLIT": ("captra_sa_fused_set_split", ()),
+    "CAPTRA_HEAD_PERSIST": ("captra_tile_bf16_set_persistent", ()),
+    "CAPTRA_L1_FINE": ("captra_sa1_stream_set_fine", ()),
+    "CAPTRA_L1_WHOLE": ("captra_sa1_stream_set_whole", ()),
+    "CAPTRA_L1_GRID": ("captra_sa1_stream_set_grid", (1,)),
 }
 
 
@@ -193,85 +238,18 @@ def lib():
                 continue  # a stale build: call() raises when the symbol is actually needed
             fn.argtypes = args
             fn.restype = _INT
-            if name in EX_ENTRY_POINTS:
+            if name in EX_ENTRY_POINTS and hasattr(l, name + "_ex"):
                 fx = getattr(l, name + "_ex")
                 fx.argtypes = args[:-1] + [_P, _P]
                 fx.restype = _INT
-        l.captra_error_string.argtypes = [_INT]
-        l.captra_error_string.restype = C.c_char_p
-        l.captra_version.restype = C.c_char_p
-        l.captra_prof_enable.argtypes = [_INT]
-        l.captra_prof_enable.restype = None
-        l.captra_prof_reset.restype = None
-        l.captra_prof_read.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
-        l.captra_prof_read.restype = _INT
-        l.captra_prof_names.argtypes = [C.c_char_p, _INT]
-        l.captra_prof_names.restype = _INT
-        for name, args in (("captra_group_points_grad_ws_bytes", [_INT] * 5), ("captra_three_interpolate_grad_ws_bytes", [_INT] * 4),
-                           ("captra_gather_points_grad_ws_bytes", [_INT] * 4)):
+        for name, (args, res) in _AUX_SIGNATURES.items():
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
-                getattr(l, name).restype = C.c_size_t
-        if hasattr(l, "captra_packed_weight_floats"):
-            l.captra_packed_weight_floats.argtypes = [_INT, _INT]
-            l.captra_packed_weight_floats.restype = _LL
-        if hasattr(l, "captra_dense_bf16_image_bytes"):
-            l.captra_dense_bf16_image_bytes.argtypes = [_INT, _INT]
-            l.captra_dense_bf16_image_bytes.restype = _LL
-            l.captra_gn_stats_bf16pm_tiles.argtypes = [_LL]
-            l.captra_gn_stats_bf16pm_tiles.restype = _INT
-            l.captra_dense_bf16_stats_tiles.argtypes = [_LL]
-            l.captra_dense_bf16_stats_tiles.restype = _INT
-        if hasattr(l, "captra_dense_bf16_tile_stats_tiles"):
-            l.captra_dense_bf16_tile_stats_tiles.argtypes = [_LL]
-            l.captra_dense_bf16_tile_stats_tiles.restype = _INT
-        if hasattr(l, "captra_chain_bf16_image_bytes"):
-            l.captra_chain_bf16_image_bytes.argtypes = [_INT, _INT]
-            l.captra_chain_bf16_image_bytes.restype = _LL
-        if hasattr(l, "captra_dense_x6_image_bytes"):
-            l.captra_dense_x6_image_bytes.argtypes = [_INT, _INT]
-            l.captra_dense_x6_image_bytes.restype = _LL
-        if hasattr(l, "captra_sa_x6_image_bytes"):
-            l.captra_sa_x6_image_bytes.argtypes = [_INT] * 4
-            l.captra_sa_x6_image_bytes.restype = _LL
-        if hasattr(l, "captra_sa_bf16_image_bytes"):
-            l.captra_sa_bf16_image_bytes.argtypes = [_INT] * 4
-            l.captra_sa_bf16_image_bytes.restype = _LL
-        if hasattr(l, "captra_sa1_stream_scratch_bytes"):
-            l.captra_sa1_stream_scratch_bytes.argtypes = [_INT, _INT]
-            l.captra_sa1_stream_scratch_bytes.restype = _LL
-            l.captra_sa1_stream_set_grid.argtypes = [_INT, _INT]
-            l.captra_sa1_stream_set_grid.restype = None
-            l.captra_sa1_stream_set_fine.argtypes = [_INT]
-            l.captra_sa1_stream_set_fine.restype = None
-            l.captra_sa1_stream_set_whole.argtypes = [_INT]
-            l.captra_sa1_stream_set_whole.restype = None
-        if hasattr(l, "captra_neck_chain_set_split"):
-            l.captra_neck_chain_set_split.argtypes = [_INT]
-            l.captra_neck_chain_set_split.restype = None
-        if hasattr(l, "captra_query_and_group_set_shape"):
-            l.captra_query_and_group_set_shape.argtypes = [_INT, _INT]
-            l.captra_query_and_group_set_shape.restype = None
-        if hasattr(l, "captra_pointwise_mlp_gn_tiles"):
-            l.captra_pointwise_mlp_gn_tiles.argtypes = [_INT, _INT, _LL]
-            l.captra_pointwise_mlp_gn_tiles.restype = _INT
-            l.captra_pointwise_mlp_gn_tiles_ex.argtypes = [_INT, _INT, _LL, _P]
-            l.captra_pointwise_mlp_gn_tiles_ex.restype = _INT
+                getattr(l, name).restype = res
         _lib = l
-        # A/B switches for measurements (thread-local knobs of the library, set for the importing thread)
-        import os
-        for env, fn in (("CAPTRA_BF16_SHARED_AFFINE", "captra_dense_bf16_set_shared_affine"), ("CAPTRA_SA_BF16_VARIANT", "captra_sa_bf16_set_variant"),
-                        ("CAPTRA_FPS_DEFER", "captra_fps_set_defer"), ("CAPTRA_NN_SPLIT", "captra_three_nn_set_split"),
-                        ("CAPTRA_BQ_CPW", "captra_ball_query_set_cpw"), ("CAPTRA_SA_SPLIT", "captra_sa_fused_set_split"),
-                        ("CAPTRA_HEAD_PERSIST", "captra_tile_bf16_set_persistent")):
-            if env in os.environ and hasattr(l, fn):
-                getattr(l, fn)(C.c_int(int(os.environ[env])))
-        if "CAPTRA_L1_FINE" in os.environ and hasattr(l, "captra_sa1_stream_set_fine"):
-            l.captra_sa1_stream_set_fine(int(os.environ["CAPTRA_L1_FINE"]))
-        if "CAPTRA_L1_WHOLE" in os.environ and hasattr(l, "captra_sa1_stream_set_whole"):
-            l.captra_sa1_stream_set_whole(int(os.environ["CAPTRA_L1_WHOLE"]))
-        if "CAPTRA_L1_GRID" in os.environ and hasattr(l, "captra_sa1_stream_set_grid"):
-            l.captra_sa1_stream_set_grid(int(os.environ["CAPTRA_L1_GRID"]), 1)
+        for env, (name, extra) in _ENV_SWITCHES.items():
+            if env in os.environ and hasattr(l, name):
+                getattr(l, name)(C.c_int(int(os.environ[env])), *extra)
     return _lib
 
 
@@ -310,7 +288,11 @@ def call(name: str, *args) -> None:
     if name in EX_ENTRY_POINTS:
         o = current_opts(name)
         if o is not None:
-            check(getattr(lib(), name + "_ex")(*args, C.byref(o), stream_ptr()), name + "_ex")
+            try:
+                fx = getattr(lib(), name + "_ex")
+            except AttributeError as e:
+                raise CaptraHipError(f"{LIB_PATH} does not export {name}_ex: rebuild it (python captra_amd/build.py)") from e
+            check(fx(*args, C.byref(o), stream_ptr()), name + "_ex")
             return
     check(fn(*args, stream_ptr()), name)
 

@@ -386,27 +386,15 @@ int launch_ball_query(int b, int n, int m, int nr, const float *radius, const in
     dim3 block(BQ_WAVES * 64);
 #define BQ_LAUNCH(NR)                                                                            \
     if (prune) {                                                                                 \
-        auto kern = ball_query_kernel<NR, true>;                                                 \
+        constexpr auto kern = ball_query_kernel<NR, true>;                                       \
         constexpr size_t extra = (size_t)(BQ_MAXCELLS + 1 + BQ_WAVES * NR * BQ_BMW) * 4 + BQ_WAVES * 6 * 4; \
         constexpr size_t cap = (size_t)BQ_PRUNE_MAXN * (12 + 16) + extra;                        \
-        static CaptraDeviceOnce once;                                                            \
-        if (once.first_use()) {                                                                  \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);           \
-            once.done();                                                                         \
-        }                                                                                        \
+        if (int e = captra_allow_lds<kern>((int)cap)) return e;                                  \
         CAPTRA_LAUNCH("ball_query", kern, grid, block, shmem + (size_t)tile_cap * 16 + extra, s, n, m, new_xyz, xyz, prm); \
     } else {                                                                                     \
-        auto kern = ball_query_kernel<NR, false>;                                                \
-        auto kern1 = ball_query_kernel<NR, false, 1>;                                            \
-        static CaptraDeviceOnce once;                                                            \
-        if (once.first_use()) {                                                                  \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, BQ_TILE * 12);       \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(kern1),                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, BQ_TILE * 12);       \
-            once.done();                                                                         \
-        }                                                                                        \
+        constexpr auto kern = ball_query_kernel<NR, false>;                                      \
+        constexpr auto kern1 = ball_query_kernel<NR, false, 1>;                                  \
+        if (int e = one ? captra_allow_lds<kern1>(BQ_TILE * 12) : captra_allow_lds<kern>(BQ_TILE * 12)) return e; \
         if (one) { CAPTRA_LAUNCH("ball_query", kern1, grid, block, shmem, s, n, m, new_xyz, xyz, prm); } \
         else { CAPTRA_LAUNCH("ball_query", kern, grid, block, shmem, s, n, m, new_xyz, xyz, prm); }     \
     }

@@ -313,21 +313,9 @@ template <int C0, int SEG, int NOCS, bool TAIL>
 int cx_launch(const CxParams &p, hipStream_t stream) {
     using S = CxShape<C0, TAIL>;
     const int lds = 3 * S::SLOTB + S::NBIAS * 4;
-    auto kern = chain_x6_kernel<C0, SEG, NOCS, TAIL>;
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return (int)hipGetLastError();
-        once.done();
-    }
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    static std::atomic<int> cus_of[128];
-    cus = cus_of[dev & 127].load(std::memory_order_relaxed);
-    if (cus == 0) {
-        hipDeviceProp_t prop;
-        cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        cus_of[dev & 127].store(cus, std::memory_order_relaxed);
-    }
+    constexpr auto kern = chain_x6_kernel<C0, SEG, NOCS, TAIL>;
+    if (int e = captra_allow_lds<kern>(lds)) return e;
+    const int cus = captra_device_cus();
     const long long njobs = ((long long)p.b * ((p.L + 31) / 32) + 3) / 4;
     const unsigned grid = (unsigned)(njobs < cus ? njobs : cus);
     CAPTRA_LAUNCH(TAIL ? "coord_tail_x6" : "mlp_chain3_x6", kern, dim3(grid), dim3(256), lds, stream, p);

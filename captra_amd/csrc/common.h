@@ -52,13 +52,13 @@ static inline bool captra_centre_window(const captra_launch_opts *o, int m, int 
 
 static inline int captra_last_error() { return (int)hipGetLastError(); }
 
-// ---- per-device one-shot (kernel function attributes) ---------------------------------------------
+// ---- per-device launch plumbing: dynamic-LDS limit, CU count, occupancy ------------------------------------------------------------
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE: a process that launches on a second GPU must set it
-// there too.  Usage:  if (once.first_use()) { hipFuncSetAttribute(...); once.done(); }
-// first_use() only LOOKS (true until done() ran for the current device): the device is marked after the attribute calls
-// returned, so a second host thread racing the first either sees the mark (attributes already applied) or applies them
-// itself (idempotent) -- it can never launch with more dynamic LDS than the attribute allows yet.  A caller that never
-// calls done() simply re-applies the attribute on every launch (correct, a few microseconds).
+// there too.  Launchers do not use this struct themselves; in front of the launch they write
+//     if (int e = captra_allow_lds<three_interpolate_kernel>(TI_LDS_BYTES)) return e;
+// first_use() only LOOKS (true until done() ran for the current device): the device is marked after the attribute call
+// returned, so a second host thread racing the first either sees the mark (attribute already applied) or applies it
+// itself (idempotent) -- it can never launch with more dynamic LDS than the attribute allows yet.
 #include <atomic>
 struct CaptraDeviceOnce {
     std::atomic<unsigned long long> seen[2] = {{0ull}, {0ull}};   // device ordinals 0..127
@@ -76,6 +76,43 @@ struct CaptraDeviceOnce {
         if (dev >= 0) seen[dev >> 6].fetch_or(1ull << (dev & 63), std::memory_order_release);
     }
 };
+
+// Let kernel `Kern` be launched with up to `bytes` of dynamic LDS on the current device: 0, or the HIP error.  The one-shot belongs
+// to the KERNEL (one per instantiation of this template), not to the call site: a launcher that picks one of several variants at run
+// time calls this for the variant it is about to launch, and none of them can go without.  A failure is not remembered (the next
+// launch tries again).
+template <auto Kern>
+int captra_allow_lds(int bytes) {
+    static CaptraDeviceOnce once;
+    if (!once.first_use()) return 0;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
+    once.done();
+    return 0;
+}
+
+// CUs of the current device (256 when the query fails), from one table per process (prof.cpp): once the device's entry is there,
+// hipGetDevice is the only runtime call -- launches happen during graph capture.
+int captra_device_cus();
+// ... minus the CUs a persistent launch leaves free (captra_launch_opts::reserved_cus), at least 1
+static inline int captra_free_cus(const captra_launch_opts *o) {
+    const int cus = captra_device_cus() - captra_reserved_cus(o);
+    return cus > 0 ? cus : 1;
+}
+
+// Workgroups of `Kern` (`threads` wide, `lds_bytes` of dynamic LDS) resident on a CU, at least 1: asked once per kernel and device,
+// AFTER captra_allow_lds<Kern> (the answer depends on the attribute).
+template <auto Kern>
+int captra_blocks_per_cu(int threads, int lds_bytes) {
+    static std::atomic<int> per_cu_of[128];
+    const int dev = CaptraDeviceOnce::device();
+    int per_cu = dev >= 0 ? per_cu_of[dev].load(std::memory_order_relaxed) : 0;
+    if (per_cu == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kern, threads, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
+        if (dev >= 0) per_cu_of[dev].store(per_cu, std::memory_order_relaxed);
+    }
+    return per_cu;
+}
 
 // debug / experiment knobs (captra_*_set_*): thread-local so that one host thread's A/B switch never changes what
 // another thread (another GPU's stream in the same process) launches; the reference boundary has no global state.

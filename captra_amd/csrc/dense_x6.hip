@@ -396,6 +396,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
+template <bool GN, bool ST, bool WREG>
+int dx_launch(const DxParams &p, unsigned grid, int lds, hipStream_t stream) {
+    constexpr auto kern = dense_x6_kernel<GN, ST, WREG>;
+    if (int e = captra_allow_lds<kern>(DX_LDS + 1024 * 8)) return e;
+    CAPTRA_LAUNCH("pointwise_mlp_x6", kern, dim3(grid), dim3(256), lds, stream, p);
+    return captra_last_error();
+}
+
 }  // namespace
 
 extern "C" long long captra_dense_x6_image_bytes(int cin, int cout) {
@@ -429,19 +437,10 @@ extern "C" int captra_pointwise_mlp_x6(int b, int cin, int cout, long long l, co
     if (grid >= (1ll << 31)) return -2;
     const int lds = DX_LDS + cin * 8;
     static const bool dx_wreg = [] { const char *e = getenv("CAPTRA_DX_WREG"); return e == nullptr || e[0] != '0'; }();
-#define DX_LAUNCH(GN_, ST_)                                                                                             \
-    do {                                                                                                                \
-        auto kern = (dx_wreg && cin % 32 == 0) ? dense_x6_kernel<GN_, ST_, true> : dense_x6_kernel<GN_, ST_, false>; \
-        static CaptraDeviceOnce once;                                                                                   \
-        if (once.first_use()) {                                                                                         \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, DX_LDS + 1024 * 8) != hipSuccess) \
-                return (int)hipGetLastError();                                                                          \
-            once.done();                                                                                                \
-        }                                                                                                               \
-        CAPTRA_LAUNCH("pointwise_mlp_x6", kern, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, p);          \
-    } while (0)
+    const bool wreg = dx_wreg && cin % 32 == 0;          // (two kernels: each is allowed its LDS by the launch that takes it)
+#define DX_LAUNCH(GN_, ST_) \
+    return wreg ? dx_launch<GN_, ST_, true>(p, (unsigned)grid, lds, (hipStream_t)stream) : dx_launch<GN_, ST_, false>(p, (unsigned)grid, lds, (hipStream_t)stream)
     if (ab_in != nullptr) { if (stats_out != nullptr) DX_LAUNCH(true, true); else DX_LAUNCH(true, false); }
     else { if (stats_out != nullptr) DX_LAUNCH(false, true); else DX_LAUNCH(false, false); }
 #undef DX_LAUNCH
-    return captra_last_error();
 }

@@ -359,12 +359,8 @@ int launch_fps(int b, int n, int m, const float *xyz, float *temp, int *idx, hip
     size_t lds_xyz = (size_t)n * 3 * sizeof(float);
     if constexpr (PPT % 2 == 0) {
         if (g_fps_variant == 0 && slots + lds_xyz <= 150 * 1024) {
-            auto kern2 = fps_kernel_blocked<NWAVES, PPT, true>;
-            static CaptraDeviceOnce once2;
-            if (once2.first_use()) {
-                hipFuncSetAttribute(reinterpret_cast<const void *>(kern2), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-                once2.done();
-            }
+            constexpr auto kern2 = fps_kernel_blocked<NWAVES, PPT, true>;
+            if (int e = captra_allow_lds<kern2>(150 * 1024)) return e;
             const size_t picks_b = (size_t)(j1 - j0) * sizeof(int);
             const int defer = (g_fps_defer && slots + lds_xyz + picks_b <= 150 * 1024) ? 1 : 0;
             CAPTRA_LAUNCH("fps", kern2, dim3(b), dim3(NWAVES * 64), slots + lds_xyz + (defer ? picks_b : 0), s, n, m, xyz, temp, idx, new_n3, new_cn, ns, defer, j0, j1);
@@ -378,13 +374,8 @@ int launch_fps(int b, int n, int m, const float *xyz, float *temp, int *idx, hip
     }
     if (need_blocked || ns != nullptr || j0 != 0 || j1 != m) return -2;  // the fused sample + gather entry (and its parts) exist on the blocked kernel only
     if (slots + lds_xyz <= 150 * 1024) {
-        auto kern = fps_kernel<NWAVES, PPT, true>;
-        static CaptraDeviceOnce once;
-        if (once.first_use()) {
-            hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            once.done();
-        }
+        constexpr auto kern = fps_kernel<NWAVES, PPT, true>;
+        if (int e = captra_allow_lds<kern>(150 * 1024)) return e;
         CAPTRA_LAUNCH("fps", kern, dim3(b), dim3(NWAVES * 64), slots + lds_xyz, s, n, m, xyz, temp, idx);
     } else {
         CAPTRA_LAUNCH("fps", (fps_kernel<NWAVES, PPT, false>), dim3(b), dim3(NWAVES * 64), slots, s, n, m,

@@ -404,19 +404,13 @@ int launch_pruned(int b, int n_stride, const int *ns, int m, const float *xyz, f
     const size_t shmem = 2 * 16 * (sizeof(uint2) + sizeof(float4)) + 6 * 16 * sizeof(float) + FP_NW * 8 * sizeof(float4) + (size_t)CAP * 2 +
                          (sort_bytes > ovf_bytes ? sort_bytes : ovf_bytes);
     constexpr int FP_T = FP_NW * 64;
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(fps_pruned_kernel<FP_NW, A, B, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipFuncSetAttribute(reinterpret_cast<const void *>(fps_pruned_kernel<FP_NW, A, B, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        once.done();
-    }
-    if (g_fps_stats != nullptr) {   // instrumented build of the same kernel (counters + s_memtime per phase)
-        CAPTRA_LAUNCH("fps", (fps_pruned_kernel<FP_NW, A, B, true>), dim3(b), dim3(FP_T), shmem, s, n_stride, ns, m, xyz, temp,
-                      idx, new_n3, new_cn, g_fps_stats);
-    } else {
+    if (g_fps_stats == nullptr) {
+        if (int e = captra_allow_lds<fps_pruned_kernel<FP_NW, A, B, false>>((int)shmem)) return e;
         CAPTRA_LAUNCH("fps", (fps_pruned_kernel<FP_NW, A, B, false>), dim3(b), dim3(FP_T), shmem, s, n_stride, ns, m, xyz, temp,
+                      idx, new_n3, new_cn, g_fps_stats);
+    } else {   // instrumented build of the same kernel (counters + s_memtime per phase)
+        if (int e = captra_allow_lds<fps_pruned_kernel<FP_NW, A, B, true>>((int)shmem)) return e;
+        CAPTRA_LAUNCH("fps", (fps_pruned_kernel<FP_NW, A, B, true>), dim3(b), dim3(FP_T), shmem, s, n_stride, ns, m, xyz, temp,
                       idx, new_n3, new_cn, g_fps_stats);
     }
     return captra_last_error();

@@ -302,14 +302,7 @@ int launch_group(int b, int c, int n, long long npos, const float *points, const
     size_t shmem = (size_t)cc * row_bytes;
     const bool vec = (npos % 4 == 0) && ((reinterpret_cast<uintptr_t>(idx) & 15) == 0) &&
                      ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(group_points_kernel<4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GP_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void *>(group_points_kernel<1>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GP_LDS_BYTES);
-        once.done();
-    }
+    if (int e = vec ? captra_allow_lds<group_points_kernel<4>>(GP_LDS_BYTES) : captra_allow_lds<group_points_kernel<1>>(GP_LDS_BYTES)) return e;
     if (vec) {
         CAPTRA_LAUNCH("group_points", group_points_kernel<4>, grid, dim3(GP_THREADS), shmem, s, c, n, npos, cc, ppb,
                       points, idx, out);
@@ -392,12 +385,7 @@ extern "C" int captra_query_and_group(int b, int n, int m, float radius, int nsa
     const size_t lds = fixed + (q.stage_rows ? (size_t)cc * n * 4 : 0);
     if (lds > 160 * 1024) return -2;
     dim3 grid((m + mcb - 1) / mcb, (ct + cs - 1) / cs, b);
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(query_and_group_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return (int)hipGetLastError();
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(query_and_group_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return (int)hipGetLastError();
-        once.done();
-    }
+    if (int e = nt != 512 ? captra_allow_lds<query_and_group_kernel<256>>(160 * 1024) : captra_allow_lds<query_and_group_kernel<512>>(160 * 1024)) return e;
     if (nt == 512) { CAPTRA_LAUNCH("query_and_group", query_and_group_kernel<512>, grid, dim3(512), lds, (hipStream_t)stream, q); }
     else { CAPTRA_LAUNCH("query_and_group", query_and_group_kernel<256>, grid, dim3(256), lds, (hipStream_t)stream, q); }
     return captra_last_error();
@@ -488,11 +476,7 @@ extern "C" int captra_group_points_multi(int b, int n, int njobs, const int *c, 
         blocks += (int)pb * ((g.c + g.cc - 1) / g.cc);
         ccmax = g.cc > ccmax ? g.cc : ccmax;
     }
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(group_points_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GP_LDS_BYTES);
-        once.done();
-    }
+    if (int e = captra_allow_lds<group_points_multi_kernel>(GP_LDS_BYTES)) return e;
     CAPTRA_LAUNCH("group_points", group_points_multi_kernel, dim3(blocks, 1, b), dim3(GP_THREADS), (size_t)ccmax * n * sizeof(float), s, m);
     return captra_last_error();
 }

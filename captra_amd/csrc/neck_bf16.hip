@@ -374,12 +374,8 @@ __global__ __launch_bounds__(NK_NT, 1) void neck_chain_kernel(NkParams p) {
 
 template <int PRO, int EPI, int MT1, int MT2, int MT3>
 int nk_launch(int b, const NkParams &p, hipStream_t s, int nz = 1) {
-    auto kern = neck_chain_kernel<PRO, EPI, MT1, MT2, MT3>;
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, NK_LDS) != hipSuccess) return (int)hipGetLastError();
-        once.done();
-    }
+    constexpr auto kern = neck_chain_kernel<PRO, EPI, MT1, MT2, MT3>;
+    if (int e = captra_allow_lds<kern>(NK_LDS)) return e;
     CAPTRA_LAUNCH("neck_chain", kern, dim3((unsigned)((p.L + NK_P - 1) / NK_P), b, nz), dim3(NK_NT), NK_LDS, s, p);
     return captra_last_error();
 }

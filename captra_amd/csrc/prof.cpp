@@ -128,6 +128,19 @@ const char *captra_version(void) { return "captra_hip 0.1 (gfx950)"; }
 }  // extern "C"
 
 
+// ---- CUs of the current device (common.h: captra_device_cus) ----------------------------------------------------------------
+int captra_device_cus() {
+    static std::atomic<int> cus_of[128];
+    const int dev = CaptraDeviceOnce::device();
+    int cus = dev >= 0 ? cus_of[dev].load(std::memory_order_relaxed) : 0;
+    if (cus == 0) {
+        if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+        if (dev >= 0) cus_of[dev].store(cus, std::memory_order_relaxed);
+    }
+    return cus;
+}
+
+
 // ---- zeroing as a kernel (common.h: captra_zero_async) ---------------------------------------------------------------------
 __global__ __launch_bounds__(256) void captra_zero_kernel(uint4 *p, size_t n16) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0u, 0u, 0u, 0u);

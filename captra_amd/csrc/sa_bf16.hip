@@ -711,12 +711,9 @@ int sb_launch(int b, SbParams p, hipStream_t stream) {
     p.njobs = b * p.jobs_per_cloud;
     if (p.njobs == 0) return 0;
     const int lds = (WLDS ? S::WBYTES : 0) + S::NBIAS * 4 + (CG >= 4 ? 4 * CG * C3 * 4 : 0);
-    auto kern = sa_bf16_kernel<CF, C1, C2, C3, K, PRE, TN, CG, WLDS, OCC, RGS, PF, DBG, LRD>;
-    static CaptraDeviceOnce once;
-    if (lds > 48 * 1024 && once.first_use()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return (int)hipGetLastError();
-        once.done();
-    }
+    constexpr auto kern = sa_bf16_kernel<CF, C1, C2, C3, K, PRE, TN, CG, WLDS, OCC, RGS, PF, DBG, LRD>;
+    if (lds > 48 * 1024)
+        if (int e = captra_allow_lds<kern>(lds)) return e;
     CAPTRA_LAUNCH("sa_scale_fused", kern, dim3((p.njobs + 3) / 4), dim3(256), lds, stream, p);
     return captra_last_error();
 }
@@ -1195,12 +1192,8 @@ __global__ __launch_bounds__(256) void bq_planes_kernel(int n, const float *__re
 
 template <int CFA, int CFB>
 int l1_launch(const L1Params &p, int grid, hipStream_t stream) {
-    auto kern = l1_stream_kernel<CFA, CFB>;
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L1_LDS) != hipSuccess) return (int)hipGetLastError();
-        once.done();
-    }
+    constexpr auto kern = l1_stream_kernel<CFA, CFB>;
+    if (int e = captra_allow_lds<kern>(L1_LDS)) return e;
     CAPTRA_LAUNCH("l1_stream", kern, dim3(grid), dim3(256), L1_LDS, stream, p);
     return captra_last_error();
 }
@@ -1272,11 +1265,9 @@ extern "C" int captra_sa1_stream_bf16(int b, int n, int m, const float *xyz_n3, 
     p.net[1].feat = cfb > 0 ? feat_b : nullptr; p.net[1].out = out_b; p.net[1].out_ctotal = 320;
     int grid = g_l1_grid;
     if (grid <= 0) {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         // up to 16 clouds one workgroup per CU: the launch then leaves room for whatever else runs (the other lane's networks), and
         // its own consumers, each alone on a CU, are not behind (bf16 step, two lanes of 16: 1.277 -> 1.23 ms; 512 workgroups: 1.43)
-        grid = (b <= 16 ? 1 : 2) * cus;
+        grid = (b <= 16 ? 1 : 2) * captra_device_cus();
     }
     if (grid < b + 1) grid = b + 1;
     if (cfa == 0 && cfb == 3) return l1_launch<0, 3>(p, grid, st);
@@ -1435,12 +1426,8 @@ template <int KST0, bool HEADS>
 int cb_launch(int b, const CbParams &p, hipStream_t stream) {
     constexpr int NF = 4 * KST0 + 64 + (HEADS ? 48 : 0), NBT = 12 + (HEADS ? 6 : 0);
     const int lds = NF * 1024 + NBT * 32 * 4;
-    auto kern = chain_bf16_kernel<KST0, HEADS>;
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return (int)hipGetLastError();
-        once.done();
-    }
+    constexpr auto kern = chain_bf16_kernel<KST0, HEADS>;
+    if (int e = captra_allow_lds<kern>(lds)) return e;
     CAPTRA_LAUNCH("mlp_chain3", kern, dim3((unsigned)((p.L + 511) / 512), b), dim3(512), lds, stream, p);
     return captra_last_error();
 }

@@ -823,17 +823,14 @@ static void sl_launch_one(const SwParams &q, unsigned grid, int lds, hipStream_t
     CAPTRA_LAUNCH("sa_scale_fused", (sa_wave_lds_kernel<CF, C1, C2, C3>), dim3(grid), dim3(SL_WAVES * 64), lds, s, q);
 }
 template <int CF>
-static void sl_launch_three(const SlRecord (&r)[3], hipStream_t s) {
+static int sl_launch_three(const SlRecord (&r)[3], hipStream_t s) {
     constexpr int lds = sl_lds_floats<CF, 64, 96, 128>() * 4;
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sa_wave_lds3_kernel<CF>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        once.done();
-    }
+    if (int e = captra_allow_lds<sa_wave_lds3_kernel<CF>>(lds)) return e;
     Sw3Params q3;
     for (int i = 0; i < 3; ++i) q3.s[i] = r[i].q;
     q3.g0 = (int)r[0].grid; q3.g1 = (int)r[1].grid;
     CAPTRA_LAUNCH("sa_scale_fused", (sa_wave_lds3_kernel<CF>), dim3(r[0].grid + r[1].grid + r[2].grid), dim3(SL_WAVES * 64), lds, s, q3);
+    return 0;
 }
 extern void captra_sp_collect_init(void *buf, size_t bytes);      // sa_pipe.hip: the second level's two scales, recorded the same way
 extern int captra_sp_collect_flush(void *buf, hipStream_t s);
@@ -842,11 +839,12 @@ static int sl_collect_flush(SlCollect &c, hipStream_t s) {
     c.n = 0;
     bool together = n == 3 && c.rec[0].cf == c.rec[1].cf && c.rec[1].cf == c.rec[2].cf;
     for (int i = 0; together && i < 3; ++i) together = c.rec[i].code == i && c.rec[i].q.dyn == nullptr;
-    if (together && c.rec[0].cf == 0) sl_launch_three<0>(c.rec, s);
-    else if (together && c.rec[0].cf == 3) sl_launch_three<3>(c.rec, s);
+    int err = 0;
+    if (together && c.rec[0].cf == 0) err = sl_launch_three<0>(c.rec, s);
+    else if (together && c.rec[0].cf == 3) err = sl_launch_three<3>(c.rec, s);
     else
         for (int i = 0; i < n; ++i) c.rec[i].launch(c.rec[i].q, c.rec[i].grid, c.rec[i].lds, s);
-    const int err = captra_last_error();
+    if (err == 0) err = captra_last_error();
     const int err2 = captra_sp_collect_flush(c.sp, s);
     return err != 0 ? err : err2;
 }
@@ -904,25 +902,11 @@ static int sa_scale_fused_impl(int b, int n, int m, int k, int cfeat, int c1, in
         // small-input scales: persistent workgroups with the weights resident in LDS (mode 2 = streaming kernel for all)
 #define SL_CASE(CF_, C1_, C2_, C3_)                                                                                   \
     if (g_sa_mode != 2 && cfeat == CF_ && c1 == C1_ && c2 == C2_ && c3 == C3_ && k % 32 == 0 && (long long)b * m < (1ll << 30)) { \
-        auto kern = sa_wave_lds_kernel<CF_, C1_, C2_, C3_>;                                                            \
+        constexpr auto kern = sa_wave_lds_kernel<CF_, C1_, C2_, C3_>;                                                  \
         constexpr int lds_bytes = sl_lds_floats<CF_, C1_, C2_, C3_>() * 4;                                             \
-        static std::atomic<int> resident_of[128];              /* per device: the attribute and the occupancy are */    \
-        int dev = 0;                                                                                                   \
-        (void)hipGetDevice(&dev);                                                                                      \
-        std::atomic<int> &resident_slot = resident_of[dev & 127];                                                      \
-        int packed = resident_slot.load(std::memory_order_relaxed);      /* workgroups per CU << 16 | CUs */           \
-        if (packed == 0) {                                                                                             \
-            int per_cu = 0;                                                                                            \
-            hipDeviceProp_t prop;                                                                                      \
-            (void)hipGetDeviceProperties(&prop, dev);                                                                  \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, SL_WAVES * 64, lds_bytes);                \
-            packed = ((per_cu > 0 ? per_cu : 1) << 16) | (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256); \
-            resident_slot.store(packed, std::memory_order_relaxed);                                                    \
-        }                                                                                                              \
-        /* (captra_launch_opts::reserved_cus: CUs another stream's samplers hold -- every persistent workgroup must be resident) */ \
-        const int cus_l = (packed & 0xffff) - captra_reserved_cus(opts) > 0 ? (packed & 0xffff) - captra_reserved_cus(opts) : 1; \
-        const int resident = (packed >> 16) * cus_l;                                                                   \
+        if (int e = captra_allow_lds<kern>(lds_bytes)) return e;                                                       \
+        /* every persistent workgroup must be resident: workgroups per CU x the CUs other streams' samplers do not hold */ \
+        const int resident = captra_blocks_per_cu<kern>(SL_WAVES * 64, lds_bytes) * captra_free_cus(opts);             \
         int wm0, wmc;                                                                                                  \
         (void)captra_centre_window(opts, m, &wm0, &wmc);                                                               \
         if (wmc == 0) return 0;                                                                                        \
@@ -980,12 +964,7 @@ static int sa_scale_fused_impl(int b, int n, int m, int k, int cfeat, int c1, in
     int wn = (2 * lds64 <= 160 * 1024) ? 2 : 1;
     if (g_sa_wn == 1 || g_sa_wn == 2) wn = g_sa_wn;
     if ((wn == 2 ? lds64 : lds32) > 160 * 1024) return -2;
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sa_fused_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sa_fused_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        once.done();
-    }
+    if (int e = wn == 1 ? captra_allow_lds<sa_fused_kernel<1>>(160 * 1024) : captra_allow_lds<sa_fused_kernel<2>>(160 * 1024)) return e;
     if (wn == 2) {
         CAPTRA_LAUNCH("sa_scale_fused", sa_fused_kernel<2>, grid, dim3(512), lds64, (hipStream_t)stream, p);
     } else {

@@ -429,16 +429,7 @@ int captra_sa_scale_pre_pm_impl(int b, int n, int m, int k, int cfeat, int c1, i
     q.b = b; q.n = n; q.m = m; q.k = k; q.v1pm = v1pm; q.xyz_cn = xyz_cn; q.new_xyz = new_xyz; q.idx = idx;
     q.w1 = w1; q.w2 = w2; q.b2 = b2; q.w3 = w3; q.b3 = b3; q.out = out; q.out_ctotal = out_ctotal; q.co_off = co_off;
     q.prof = captra_sa_prof_ptr();
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    static std::atomic<int> cus_of[128];
-    cus = cus_of[dev & 127].load(std::memory_order_relaxed);
-    if (cus == 0) {
-        hipDeviceProp_t prop;
-        cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        cus_of[dev & 127].store(cus, std::memory_order_relaxed);
-    }
-    cus = cus - captra_reserved_cus(opts) > 0 ? cus - captra_reserved_cus(opts) : 1;     // (captra_launch_opts::reserved_cus)
+    const int cus = captra_free_cus(opts);               // (captra_launch_opts::reserved_cus)
     // one workgroup (4 waves, one per SIMD) per CU; a wave per centre
     const long long centres = (long long)b * m;
     if (centres >= (1ll << 30)) return -2;

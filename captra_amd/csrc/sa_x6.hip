@@ -535,21 +535,10 @@ template <int CF, int C1, int C2, int C3, bool PRE, bool RING, int WAVES>
 int sx_launch(const SxParams &p, hipStream_t stream) {
     using S = SxShape<CF, C1, C2, C3, PRE>;
     const int lds = (RING ? 3 * S::SLOTB : S::WBYTES) + S::NBIAS * 4;
-    auto kern = sa_x6_kernel<CF, C1, C2, C3, PRE, RING, WAVES>;
-    static CaptraDeviceOnce once;
-    if (lds > 48 * 1024 && once.first_use()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return (int)hipGetLastError();
-        once.done();
-    }
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    static std::atomic<int> cus_of[128];
-    cus = cus_of[dev & 127].load(std::memory_order_relaxed);
-    if (cus == 0) {
-        hipDeviceProp_t prop;
-        cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        cus_of[dev & 127].store(cus, std::memory_order_relaxed);
-    }
+    constexpr auto kern = sa_x6_kernel<CF, C1, C2, C3, PRE, RING, WAVES>;
+    if (lds > 48 * 1024)
+        if (int e = captra_allow_lds<kern>(lds)) return e;
+    const int cus = captra_device_cus();
     const long long njobs = ((long long)p.b * p.m + WAVES - 1) / WAVES;
     const int per_cu = 1;                               // (the register budget is cut for WAVES / 4 waves per SIMD: one workgroup per CU)
     const unsigned grid = (unsigned)(njobs < (long long)cus * per_cu ? njobs : (long long)cus * per_cu);

@@ -155,25 +155,14 @@ int captra_scatter_reduce(bool interp, int b, int c, int n_src, long long npos, 
     if (workspace == nullptr || workspace_bytes < need) return (int)hipErrorInvalidValue;
     int *ws = static_cast<int *>(workspace);
     int *start = ws, *order = ws + (size_t)b * (n_src + 1);
-    static CaptraDeviceOnce once;
-    if (once.first_use()) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(build_csr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            CSR_MAX_SRC * (int)sizeof(int));
-        once.done();
-    }
+    if (int e = captra_allow_lds<build_csr_kernel>(CSR_MAX_SRC * (int)sizeof(int))) return e;
     CAPTRA_LAUNCH("scatter_csr", build_csr_kernel, dim3(b), dim3(CSR_T), (size_t)n_src * sizeof(int), s, n_src, (int)npos, idx,
                   start, order);
     dim3 grid((n_src + 255) / 256, (c + SR_CH - 1) / SR_CH, b);
     const int row_len = interp ? (int)(npos / 3) : (int)npos;
     if (row_len <= 16384 && c >= 8) {
-        static CaptraDeviceOnce once_lds;
-        if (once_lds.first_use()) {
-            hipFuncSetAttribute(reinterpret_cast<const void *>(scatter_reduce_lds_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * (int)sizeof(float));
-            hipFuncSetAttribute(reinterpret_cast<const void *>(scatter_reduce_lds_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * (int)sizeof(float));
-            once_lds.done();
-        }
+        constexpr int row_cap = 16384 * (int)sizeof(float);
+        if (int e = interp ? captra_allow_lds<scatter_reduce_lds_kernel<true>>(row_cap) : captra_allow_lds<scatter_reduce_lds_kernel<false>>(row_cap)) return e;
         int cpb = 1;
         while ((long long)((c + cpb - 1) / cpb) * b > 1024 && cpb < 16) cpb *= 2;   // ~2-4 workgroups per CU
         dim3 g2((c + cpb - 1) / cpb, b);

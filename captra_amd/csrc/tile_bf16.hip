@@ -673,19 +673,12 @@ template <int MT, int NW, int IN, bool AFF, int OUT, bool ST>
 int tb_launch(int b, const TbParams &p, hipStream_t s) {
     dim3 grid((unsigned)((p.L + TB_P - 1) / TB_P), (p.nt + NW * MT - 1) / (NW * MT), b);
     const int lds = 2 * TB_CHUNK + (AFF ? p.kst * 128 : 0);
-    static CaptraDeviceOnce once_f, once_p;
     constexpr bool CAN_KF = IN == 0 && OUT == 0;
     if (CAN_KF && p.kst % 8 == 0) {
-        if (once_f.first_use()) {
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&tb_layer_kernel<MT, NW, IN, AFF, OUT, ST, CAN_KF>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_CHUNK + 65536);
-            once_f.done();
-        }
+        if (int e = captra_allow_lds<tb_layer_kernel<MT, NW, IN, AFF, OUT, ST, CAN_KF>>(2 * TB_CHUNK + 65536)) return e;
         CAPTRA_LAUNCH("pointwise_mlp", (tb_layer_kernel<MT, NW, IN, AFF, OUT, ST, CAN_KF>), grid, dim3(NW * 64), lds, s, p);
     } else {
-        if (once_p.first_use()) {
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&tb_layer_kernel<MT, NW, IN, AFF, OUT, ST, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_CHUNK + 65536);
-            once_p.done();
-        }
+        if (int e = captra_allow_lds<tb_layer_kernel<MT, NW, IN, AFF, OUT, ST, false>>(2 * TB_CHUNK + 65536)) return e;
         CAPTRA_LAUNCH("pointwise_mlp", (tb_layer_kernel<MT, NW, IN, AFF, OUT, ST, false>), grid, dim3(NW * 64), lds, s, p);
     }
     return captra_last_error();
@@ -830,19 +823,7 @@ extern "C" int captra_head12_bf16_ex(int b, int cin, long long l, const void *x,
         CAPTRA_LAUNCH("pointwise_mlp", tb_head12_kernel<0>, grid, dim3(512), 32768, s, p);
         return captra_last_error();
     }
-    static CaptraDeviceOnce once;
-    static std::atomic<int> cus_of[128];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (once.first_use()) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&tb_head12_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&tb_head12p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 8192);
-        hipDeviceProp_t prop;
-        cus_of[dev & 127].store((hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256);
-        once.done();
-    }
-    const int cus_dev = cus_of[dev & 127].load() > 0 ? cus_of[dev & 127].load() : 256;
-    const int cus = cus_dev - captra_reserved_cus(opts) > 0 ? cus_dev - captra_reserved_cus(opts) : 1;      // (captra_launch_opts::reserved_cus)
+    const int cus = captra_free_cus(opts);               // (captra_launch_opts::reserved_cus)
     const long long tpc = (l + TB_P - 1) / TB_P, ntiles = (long long)b * tpc;
     if (g_tb_persist && ntiles > cus && ntiles < (1ll << 30)) {
         // persistent: one workgroup per CU, contiguous runs of tiles
@@ -850,9 +831,11 @@ extern "C" int captra_head12_bf16_ex(int b, int cin, long long l, const void *x,
         pp.q = p; pp.tpc = (int)tpc; pp.ntiles = (int)ntiles;
         pp.tpw = (int)((ntiles + cus - 1) / cus);
         const int nwg = (int)((ntiles + pp.tpw - 1) / pp.tpw);
+        if (int e = captra_allow_lds<tb_head12p_kernel>(131072 + 8192)) return e;
         CAPTRA_LAUNCH("pointwise_mlp", tb_head12p_kernel, dim3(nwg), dim3(512), 131072 + 8192, s, pp);
         return captra_last_error();
     }
+    if (int e = captra_allow_lds<tb_head12_kernel<1>>(131072)) return e;
     CAPTRA_LAUNCH("pointwise_mlp", tb_head12_kernel<1>, grid, dim3(512), 131072, s, p);
     return captra_last_error();
 }

@@ -66,7 +66,6 @@ SPLIT_K_POSITIONS = int(os.environ.get("CAPTRA_SPLIT_K_POSITIONS", "8192"))    #
 # k.  Measured (tools/ab_round6.sh, 32 trajectories in two lanes, same box): 3.376 ms off, 3.378 at 2048 positions, 3.40-3.41 at 8192 /
 # 16384 -- the other lane's kernels already fill the chip under those chains and the 32 x 32 split tiles re-read more.  Off.
 X6_SPLIT_K_POSITIONS = int(os.environ.get("CAPTRA_X6_SPLIT_K_POSITIONS", "0"))
-_split_k_on = False          # (kept for readers of the module attribute; the live flag is per thread: _split_k_active())
 
 
 def _split_k_active() -> bool:

@@ -37,8 +37,26 @@ def test_library_exports_every_declared_symbol():
 def test_python_binding_table_matches_header():
     from captra_amd import _lib
     syms = set(declared_symbols())
-    for name in _lib._SIGNATURES:
+    for name in list(_lib._SIGNATURES) + list(_lib._AUX_SIGNATURES):
         assert name in syms, f"{name} bound in _lib.py but not declared in the header"
+    assert not set(_lib._SIGNATURES) & set(_lib._AUX_SIGNATURES)
+    for name in _lib.EX_ENTRY_POINTS:
+        assert name in _lib._SIGNATURES and name + "_ex" in syms
+
+
+def test_launch_plumbing_lives_in_common_h():
+    """Per-device kernel attributes, the CU count and the occupancy query are common.h / prof.cpp's (captra_allow_lds,
+    captra_device_cus, captra_free_cus, captra_blocks_per_cu): no kernel family carries a copy of its own."""
+    csrc = ROOT / "captra_amd" / "csrc"
+    banned = ("hipFuncSetAttribute", "hipGetDeviceProperties", "hipOccupancyMaxActiveBlocksPerMultiprocessor", "CaptraDeviceOnce",
+              "hipDeviceGetAttribute")
+    hips = sorted(csrc.glob("*.hip"))
+    assert hips
+    bad = [(p.name, word) for p in hips for word in banned if word in p.read_text()]
+    assert not bad, bad
+    others = [p.name for p in sorted(csrc.iterdir()) if p.suffix in (".h", ".cpp") and p.name not in ("common.h", "prof.cpp")
+              and "hipDeviceGetAttribute" in p.read_text()]
+    assert not others, others
 
 
 def test_pointnet2_cuda_module_surface():
