@@ -13,6 +13,8 @@ import os
 
 import torch
 
+from . import fused
+
 
 # The streams the lanes of the re-crop loop run on: lane l's MAIN stream and the SIDE stream its RotationNet branch runs on,
 # created ONCE per process and device, back to back.  Which hardware queue a HIP stream feeds is decided when it is created
@@ -41,6 +43,15 @@ def lane_streams(dev, lanes: int = 2):
     return have[:lanes]
 
 
+def step_inputs(points, points_mean, labels=None):
+    """The (input, npcs_input) dict pair EvalTrackModel.track_step takes, over one cloud."""
+    input = {"points": points, "points_mean": points_mean, "meta": {}}
+    npcs_input = {"points": points, "points_mean": points_mean}
+    if labels is not None:
+        input["labels"] = npcs_input["labels"] = labels
+    return input, npcs_input
+
+
 class TrackStepGraph:
     def __init__(self, model, points: torch.Tensor, points_mean: torch.Tensor, pose: dict, labels: torch.Tensor | None = None,
                  warmup: int = 2, split_side=None, allow_split_k: bool = True):
@@ -50,7 +61,7 @@ class TrackStepGraph:
         self.model = model
         self.split_side = split_side
         # a LANE of a larger batch (TrackLanes) must compute what the whole batch computes: the few-trajectory split-k rule of
-        # EvalTrackModel._track_step goes by the batch it sees, so it is switched off for sub-batches
+        # EvalTrackModel._step_context goes by the batch it sees, so it is switched off for sub-batches
         self.allow_split_k = allow_split_k
         dev = points.device
         self.points = points.clone()
@@ -92,12 +103,8 @@ class TrackStepGraph:
     def _capture_split(self) -> bool:
         """[prep] -> [rot || coord] -> [post] as four linear graphs.  RotationNet's graph allocates from a pool of its own: it
         replays beside CoordinateNet's, so memory one of them frees while being captured must not be handed to the other."""
-        from . import fused
         m = self.model
-        inp = {"points": self.points, "points_mean": self.points_mean, "meta": {}}
-        npcs_in = {"points": self.points, "points_mean": self.points_mean}
-        if self.labels is not None:
-            inp["labels"] = npcs_in["labels"] = self.labels
+        inp, npcs_in = step_inputs(self.points, self.points_mean, self.labels)
         if not m._overlap_nets(inp):
             return False
         cap = torch.cuda.Stream(device=self.points.device)
@@ -105,11 +112,8 @@ class TrackStepGraph:
         self._graphs = [torch.cuda.CUDAGraph() for _ in range(4)]
         state = {}
 
-        with fused.use_mlp_dtype(m.mlp_dtype):
-            few = fused.split_k_rule(len(self.points), allow_few=self.allow_split_k)     # (as EvalTrackModel._track_step)
-
         def capture(g, pool, fn):
-            with torch.cuda.graph(g, pool=pool, stream=cap, capture_error_mode="thread_local"), torch.no_grad(), fused.use_mlp_dtype(m.mlp_dtype), fused.split_k(few):
+            with torch.cuda.graph(g, pool=pool, stream=cap, capture_error_mode="thread_local"), torch.no_grad(), m._step_context(self.points, self.allow_split_k):
                 return fn()
 
         def prep():
@@ -147,17 +151,7 @@ class TrackStepGraph:
         g_post.replay()
 
     def _step(self):
-        input = {"points": self.points, "points_mean": self.points_mean, "meta": {}}
-        npcs_input = {"points": self.points, "points_mean": self.points_mean}
-        if self.labels is not None:
-            input["labels"] = self.labels
-            npcs_input["labels"] = self.labels
-        prev = getattr(self.model, "_no_split_k", False)
-        self.model._no_split_k = prev or not self.allow_split_k
-        try:
-            return self.model.track_step(input, npcs_input, self.pose)
-        finally:
-            self.model._no_split_k = prev
+        return self.model.track_step(*step_inputs(self.points, self.points_mean, self.labels), self.pose, allow_split_k=self.allow_split_k)
 
     def stale(self) -> bool:
         """True when a module UNDER THIS GRAPH'S MODEL re-folded (or dropped) its weights after the capture: the replay would
@@ -188,13 +182,18 @@ class TrackStepGraph:
             pairs.append((labels, self.labels))
         # the step's inputs into the captured buffers: one launch when they are plain device tensors of the captured types
         if all(a.is_cuda and a.is_contiguous() and a.dtype == b.dtype and a.shape == b.shape and a.element_size() % 4 == 0 for a, b in pairs):
-            from . import fused
             fused.copy_multi(pairs)
         else:
             for a, b in pairs:
                 b.copy_(a)
         self._replay_graphs()
         return self.out_pose
+
+    def replay_cloned(self, points, points_mean, pose):
+        """`replay`, with CoordinateNet's maps and the pose cloned out of the static buffers -> (npcs_pred, pose)."""
+        out = self.replay(points, points_mean, pose)
+        npcs = {k: v.clone() for k, v in self.npcs_pred.items() if torch.is_tensor(v)}
+        return npcs, {k: v.clone() for k, v in out.items()}
 
 
 class TrackLanes:
@@ -247,7 +246,6 @@ class TrackLanes:
         """Enqueue one frame on every lane; returns the ring slot its poses will be in.  The frame's inputs must already be
         resident; if the caller's stream is still producing them pass sync_inputs=True (the lanes then wait for that
         stream, which joins them whenever it also carries the previous frame's gather)."""
-        from . import fused
         self._mark_consumed()
         slot = self.frame % len(self.ring)
         self.frame += 1

@@ -10,11 +10,13 @@ Mirrors the contract of the reference's network/models/model.py: `BaseModel` (l.
 Frame i consumes the pose predicted for frame i-1 (strictly sequential, model.py:408-478);
 trajectories of one batch are independent, which is what shards over GPUs (parallel.py).
 
-Out of scope here (SURVEY.md §8f "next"): the on-the-fly depth crop of `nocs_otf` (model.py:425-452,
-needs cv2 + the dataset) and the IoU/segmentation losses of compute_loss (loss.py, bbox_utils.py).
+The on-the-fly depth crop of `nocs_otf` (model.py:425-452) runs on the device from pre-fetched depth / mask tensors
+(captra_amd/nocs_otf.py; reading the images from disk is the data loader's); compute_loss carries the reference's
+segmentation, NOCS and box-IoU figures (loss.py, bbox_utils.py).
 """
 from __future__ import annotations
 
+import contextlib
 import pickle
 from copy import deepcopy
 from os.path import join as pjoin
@@ -25,7 +27,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .networks import CoordNet, PartCanonNet
+from . import fused
+from . import graph as G
+from .networks import CoordNet, PartCanonNet, _canonicalize
 from .pose_utils.part_dof_utils import add_noise_to_part_dof, consume_noise_draws, eval_part_full, part_model_batch_to_part
 from .utils import Timer, add_dict, cvt_torch, divide_dict, ensure_dirs, get_ith_from_batch
 
@@ -96,7 +100,11 @@ def _otf_bound(longest: int, n: int) -> int:
 
 
 OTF_POSE_ON_DEVICE = os.environ.get("CAPTRA_OTF_POSE_ON_DEVICE", "1") != "0"   # nocs_otf: the crop box from the device-resident pose (A/B: 0 = via the host)
-_OTF_LANE_STREAMS: dict = {}      # device index -> the two lane streams of EvalTrackModel._forward_otf_lanes
+_OTF_LANE_STREAMS: dict = {}      # device index -> the two lane streams of EvalTrackModel._otf_lane_frames
+
+
+def _frame_names(frame):
+    return [p.split(".")[-2].split("/")[-1] for p in frame["meta"]["path"]]
 
 
 class EvalTrackModel(BaseModel):
@@ -142,7 +150,7 @@ class EvalTrackModel(BaseModel):
         # write (rank 0 writes the pickles of every rank's trajectories).  Both None = the single-process behaviour.
         self.frame_hook = None
         self.result_sink = None
-        # nocs_otf at batch >= 32 as two lanes half a frame apart (_forward_otf_lanes): bit-identical results, 9.5 -> 7.9 ms per
+        # nocs_otf at batch >= 32 as two lanes half a frame apart (_otf_lane_frames): bit-identical results, 9.5 -> 7.9 ms per
         # 32-trajectory step (3370 -> 4060 frames/s).  On by default (cfg['otf_lanes'] = False turns it off): with the lane
         # streams created once per process the first eight model objects of a process all get the fast placement; what a
         # later one may get (both lanes on one hardware queue, ~13 ms) is in DESIGN.md section 5
@@ -203,32 +211,31 @@ class EvalTrackModel(BaseModel):
             part["translation"], part["scale"] = crop["translation"], crop["scale"]
         return part
 
-    def track_step(self, input, npcs_input, last_pose):
-        """One frame for all B trajectories: CoordNet -> labels -> RotationNet -> pose fit."""
-        from . import fused
+    @contextlib.contextmanager
+    def _step_context(self, points, allow_split_k=True):
+        """What every launch of a step over the clouds `points` (B,3,N) runs under: this model's MLP arithmetic and the split-k
+        limit that goes with B.  allow_split_k=False: a lane of a larger batch, which must compute what the whole batch computes
+        at any size, so it never takes the few-trajectory form."""
         with fused.use_mlp_dtype(self.mlp_dtype):
-            return self._track_step(input, npcs_input, last_pose)
+            few = fused.split_k_rule(len(points), allow_few=allow_split_k) if not self.training and points.is_cuda else 0
+            with fused.split_k(few):
+                yield
 
-    def _track_step(self, input, npcs_input, last_pose):
-        from . import fused
-        few = (fused.split_k_rule(len(input["points"]), allow_few=not getattr(self, "_no_split_k", False))
-               if not self.training and input["points"].is_cuda else 0)
-        with fused.split_k(few):
-            return self._track_step_body(input, npcs_input, last_pose)
+    def track_step(self, input, npcs_input, last_pose, allow_split_k=True):
+        """One frame for all B trajectories: CoordNet -> labels -> RotationNet -> pose fit."""
+        with self._step_context(input["points"], allow_split_k):
+            self._step_begin(input, npcs_input, last_pose)
+            join = self._fork_rotation_net(input, npcs_input, last_pose) if self._overlap_nets(input) else None
+            if join is None and "_geom" not in npcs_input and self._l1_stream_on(npcs_input):
+                # networks one after the other (no fork): the shared prefix with the level-1 stream kernel all the same --
+                # CoordinateNet takes it from `_geom`, RotationNet through the shared geometry
+                self._step_prep(input, npcs_input, last_pose)
+            npcs_pred = self._step_coord(npcs_input)
+            if join is not None:
+                join()
+            return npcs_pred, self._step_post(input, npcs_input, npcs_pred, last_pose)
 
-    def _track_step_body(self, input, npcs_input, last_pose):
-        self._step_begin(input, npcs_input, last_pose)
-        join = self._fork_rotation_net(input, npcs_input, last_pose) if self._overlap_nets(input) else None
-        if join is None and "_geom" not in npcs_input and self._l1_stream_on(npcs_input):
-            # networks one after the other (no fork): the shared prefix with the level-1 stream kernel all the same -- CoordinateNet
-            # takes it from `_geom`, RotationNet through the shared geometry
-            self._step_prep(input, npcs_input, last_pose)
-        npcs_pred = self._step_coord(npcs_input)
-        if join is not None:
-            join()
-        return npcs_pred, self._step_post(input, npcs_input, npcs_pred, last_pose)
-
-    # ---- the step in four phases (what `_track_step` composes; captra_amd.graph.TrackStepGraph(split=True) captures each as a
+    # ---- the step in four phases (what `track_step` composes; captra_amd.graph.TrackStepGraph(split=True) captures each as a
     # hipGraph of its own and replays [prep] -> [rot || coord] -> [post] on two EXPLICIT streams) ---------------------------
     def _step_begin(self, input, npcs_input, last_pose):
         # (a view when it is contiguous -- one part: the clones are three copy kernels per step and nothing writes into them)
@@ -242,18 +249,15 @@ class EvalTrackModel(BaseModel):
     def _step_prep(self, input, npcs_input, last_pose, level1_only=False, side=None) -> bool:
         """The part both networks wait for: CoordinateNet's canonicalised cloud and its geometry (sampling, neighbour lists,
         interpolation weights).  False when the cloud does not fit the one-launch sampler (no side-by-side schedule then)."""
-        from . import fused
-        from .networks import _canonicalize
         coord_bb = self.npcs_net.backbone
         # bf16 mode, one part: both networks' first level inside the sampler's launch (the level-1 stream kernel)
         stream = self._l1_stream_on(npcs_input)
         cam = _canonicalize(npcs_input["points"], npcs_input["points_mean"], npcs_input["canon_pose"], want_planes=stream)
         stream_level1 = None
         if stream:
-            # RotationNet's backbone sees the bare coordinates, CoordinateNet's the coordinates as features too (use_xyz_feat)
-            # RotationNet's backbone sees the bare coordinates, CoordinateNet's the coordinates as features too.  CAPTRA_L1_NETS=rot
-            # (A/B): RotationNet's level only, CoordinateNet's three scales as launches of its own branch -- measured equal at 32
-            # trajectories (1.27 ms per step either way: the step is bound by the chip's work, not by the sampler's latency)
+            # RotationNet's backbone sees the bare coordinates, CoordinateNet's the coordinates as features too (use_xyz_feat).
+            # CAPTRA_L1_NETS=rot (A/B): RotationNet's level only, CoordinateNet's three scales as launches of its own branch -- measured
+            # equal at 32 trajectories (1.27 ms per step either way: the step is bound by the chip's work, not by the sampler's latency)
             nets = [(self.net.regress_net.encoder, None)]
             if os.environ.get("CAPTRA_L1_NETS", "both") == "both":
                 nets.append((coord_bb, cam[0]))
@@ -278,7 +282,6 @@ class EvalTrackModel(BaseModel):
 
     def _l1_stream_on(self, npcs_input) -> bool:
         """bf16 mode, one part: both networks' first level inside the sampler's launch (the level-1 stream kernel)."""
-        from . import fused
         pts = npcs_input["points"]
         return (self.l1_stream and self.num_parts == 1 and self.share_geometry and fused.USE_L1_STREAM and fused.mlp_dtype() == "bf16"
                 and not self.training and pts.is_cuda and pts.shape[2] <= 4096 and pts.shape[0] <= fused.L1_STREAM_MAX_CLOUDS
@@ -287,7 +290,6 @@ class EvalTrackModel(BaseModel):
     def check_l1_stream(self) -> None:
         """Raises when a consumer of ANY level-1 stream launch since the last check gave up waiting for its sampler (bounded spins;
         synchronises): the sticky word every step ORs its flag into, then the last launch's own flag."""
-        from . import fused
         sticky = getattr(self, "_l1_sticky", None)
         scratch = getattr(self, "_l1_scratch", None)
         bad = (sticky is not None and bool(sticky.item())) or (scratch is not None and fused.sa1_stream_gave_up(scratch))
@@ -299,7 +301,6 @@ class EvalTrackModel(BaseModel):
 
     def _step_rot(self, input, npcs_input, last_pose):
         """RotationNet up to its heads' raw per-point output (needs nothing of CoordinateNet's but, for one part, its geometry)."""
-        from .networks import _canonicalize
         P = self.num_parts
         cam, geom = npcs_input["_canon"], npcs_input["_geom"]
         if P == 1 and self.share_geometry:            # one part: RotationNet's cloud IS CoordinateNet's
@@ -336,7 +337,6 @@ class EvalTrackModel(BaseModel):
         """The two backbones do not depend on each other (RotationNet needs CoordNet's labels only for its read-out): they
         run on two streams = two branches of the captured graph, each filling the other's latency-bound stretches and
         launch ramps / tails.  1.37 -> 1.18 ms per frame at one trajectory, 6.56 -> 6.40 ms per step at 32."""
-        from . import fused
         return (self.overlap_nets
                 and not self.training and input["points"].is_cuda and fused.USE_ROT_READOUT
                 and not (self.track_cfg["gt_label"] or self.track_cfg["nocs2d_label"]) and not self.net.return_point_rotation)
@@ -352,7 +352,6 @@ class EvalTrackModel(BaseModel):
         if self.sampler_chunks > 1 and self.num_parts == 1 and self.share_geometry:
             # the geometry on a stream of its own, both networks forked right behind the canonicalisation: their first level
             # waits for the sampler's parts one by one, their second level for the rest of the geometry
-            from .networks import _canonicalize
             if getattr(self, "_gstream", None) is None:
                 self._gstream = torch.cuda.Stream(device=dev)
             cam = _canonicalize(npcs_input["points"], npcs_input["points_mean"], npcs_input["canon_pose"])
@@ -379,33 +378,26 @@ class EvalTrackModel(BaseModel):
         return (self.use_graph and not self.training and input["points"].is_cuda
                 and not (self.track_cfg["gt_label"] or self.track_cfg["nocs2d_label"]))
 
+    def _cached(self, key, build):
+        """The captured object of this batch form (`self._graph`: a TrackStepGraph, a TrackLanes, or the re-crop lanes' list of
+        TrackStepGraph), built when there is none, when it was captured for another `key`, or when a weight under it changed."""
+        g = self._graph
+        if g is None or self._graph_key != key or any(x.stale() for x in (g if isinstance(g, list) else [g])):
+            self._graph, self._graph_key = build(), key
+        return self._graph
+
     def _graph_step(self, input, last_pose):
         """One frame through the captured graph (captured on first use for this batch shape); outputs are cloned out
         of the graph's static buffers."""
-        from .graph import TrackStepGraph
-        key = (tuple(input["points"].shape), str(input["points"].device))
-        if self._graph is None or self._graph_key != key or self._graph.stale():
-            self._graph = TrackStepGraph(self, input["points"], input["points_mean"], last_pose)
-            self._graph_key = key
-        pose = self._graph.replay(input["points"], input["points_mean"], last_pose)
-        npcs = {k: v.clone() for k, v in self._graph.npcs_pred.items() if torch.is_tensor(v)}
-        return npcs, {k: v.clone() for k, v in pose.items()}
+        points, mean = input["points"], input["points_mean"]
+        graph = self._cached((tuple(points.shape), str(points.device)), lambda: G.TrackStepGraph(self, points, mean, last_pose))
+        return graph.replay_cloned(points, mean, last_pose)
 
     def _lanes_usable(self, input) -> bool:
         """From 32 trajectories on the captured step runs as two free-running lanes (graph.TrackLanes; +2.8 % frames/s,
         -1 % at 8 and 16).  Not with the on-the-fly re-crop: it reads the previous pose on the host every frame."""
         B = input["points"].shape[0]
         return self._graph_usable(input) and not self.nocs_otf and B >= 32 and B % 2 == 0
-
-    def _lanes_for(self, input, pose):
-        from .graph import TrackLanes
-        key = ("lanes", tuple(input["points"].shape), str(input["points"].device))
-        if self._graph is None or self._graph_key != key or self._graph.stale():
-            self._graph = TrackLanes(self, input["points"], input["points_mean"], pose, lanes=2, keep_npcs=True)
-            self._graph_key = key
-        else:
-            self._graph.set_pose(pose)
-        return self._graph
 
     def _recrop_slice(self, i, input, last_pose, sl, defer=None):
         """nocs_otf (reference model.py:425-452) for the trajectories `sl` of frame i: re-crop around the pose predicted for
@@ -470,15 +462,15 @@ class EvalTrackModel(BaseModel):
         return (self.nocs_otf and input["points"].is_cuda and not self.training and B >= 32 and B % 2 == 0
                 and not (self.track_cfg["gt_label"] or self.track_cfg["nocs2d_label"]))
 
-    def _forward_otf_lanes(self, pose0, frame_nums):
-        from .graph import TrackStepGraph
+    def _otf_lane_frames(self, pose0):
+        """The frame closures of `forward` for the two re-crop lanes (`_otf_lanes_usable`): each lane re-crops its half of the
+        batch and runs its step on a stream of its own; `commit` assembles the batch-wide tensors on the caller's stream."""
         feed = self.feed_dict
         B = feed[1]["points"].shape[0]
         half = B // 2
         slices = [slice(0, half), slice(half, B)]
         dev = feed[1]["points"].device
         cur = torch.cuda.current_stream(dev)
-        from . import graph as G
         if G.SPLIT_OTF_LANES:
             pairs = G.lane_streams(dev, 2)       # process-wide explicit streams: see captra_amd/graph.py SPLIT_OTF_LANES
             streams, sides = [m_ for m_, _ in pairs], [s_ for _, s_ in pairs]
@@ -489,26 +481,19 @@ class EvalTrackModel(BaseModel):
                     _OTF_LANE_STREAMS[key] = [torch.cuda.Stream(device=dev) for _ in slices]
                 self._otf_streams = _OTF_LANE_STREAMS[key]
             streams, sides = self._otf_streams, [None, None]
-        use_graph = self._graph_usable(feed[1])
         graphs = None
-        if use_graph:
-            key = ("otf", tuple(feed[1]["points"].shape), str(dev))
-            if self._graph is None or self._graph_key != key or any(g.stale() for g in self._graph):
-                self._graph = [TrackStepGraph(self, feed[1]["points"][s].contiguous(), feed[1]["points_mean"][s].contiguous(),
-                                              {k: v[s].contiguous() for k, v in pose0.items()}, split_side=side, allow_split_k=False) for s, side in zip(slices, sides)]
-                self._graph_key = key
-            graphs = self._graph
+        if self._graph_usable(feed[1]):
+            graphs = self._cached(("otf", tuple(feed[1]["points"].shape), str(dev)), lambda: [
+                G.TrackStepGraph(self, feed[1]["points"][s].contiguous(), feed[1]["points_mean"][s].contiguous(),
+                                 {k: v[s].contiguous() for k, v in pose0.items()}, split_side=side, allow_split_k=False) for s, side in zip(slices, sides)])
         lane_pose = [{k: v[s].clone() for k, v in pose0.items()} for s in slices]
         for st in streams:
             st.wait_stream(cur)
-        pred_poses, npcs_pred = [pose0], [None]
         state = {"sampled": None}      # recorded on a lane's stream when its re-crop (crop + sampling launch) of the current frame is enqueued
-        N = feed[1]["points"].shape[2]
-        defer_ok = self._otf_defer_usable(feed[1])
 
         def run_frame(i, poses_in, bounds):
             """Frame i of both lanes from the poses entering it; bounds[l] = the sync-free re-crop's stride bound of lane l or None
-            (the synchronous stage).  -> (parts, events, poses out, deferred checks)."""
+            (the synchronous stage).  -> ((parts, events), poses out, deferred checks)."""
             input = feed[i]
             parts, done, poses_out, checks = [], [], [], []
             for l, s in enumerate(slices):
@@ -523,28 +508,26 @@ class EvalTrackModel(BaseModel):
                             state["sampled"].synchronize()
                     res = self._recrop_slice(i, input, poses_in[l], s, defer=bounds[l])
                     pts, labels, nocs = res[:3]
-                    checks.append(_OtfCheck(res[3]) if len(res) > 3 and res[3] is not None else None)
+                    if len(res) > 3 and res[3] is not None:
+                        checks.append(_OtfCheck(res[3]))
                     state["sampled"] = torch.cuda.Event()
                     state["sampled"].record(streams[l])
                     mean = input["points_mean"][s]
                     if graphs is not None:
-                        out = graphs[l].replay(pts, mean, poses_in[l])
-                        pose = {k: v.clone() for k, v in out.items()}
-                        cur_npcs = {k: v.clone() for k, v in graphs[l].npcs_pred.items() if torch.is_tensor(v)}
+                        cur_npcs, pose = graphs[l].replay_cloned(pts, mean, poses_in[l])
                     else:
-                        lin = {"points": pts, "points_mean": mean, "meta": {}, "labels": labels}
-                        lnp = {"points": pts, "points_mean": mean, "labels": labels}
-                        cur_npcs, pose = self.track_step(lin, lnp, poses_in[l])
+                        cur_npcs, pose = self.track_step(*G.step_inputs(pts, mean, labels), poses_in[l])
                         cur_npcs = {k: v for k, v in cur_npcs.items() if torch.is_tensor(v)}
                     poses_out.append(pose)
                     ev = torch.cuda.Event()
                     ev.record(streams[l])
                 parts.append((pts, labels, nocs, pose, cur_npcs))
                 done.append(ev)
-            return parts, done, poses_out, checks
+            return (parts, done), poses_out, checks
 
-        def commit(i, parts, done, replace):
+        def commit(i, result):
             """The frame's batch-wide tensors, assembled on the caller's stream (GPU-side waits: the lanes do not stop)."""
+            parts, done = result
             input, npcs_in = feed[i], self.npcs_feed_dict[i]
             for ev in done:
                 cur.wait_event(ev)
@@ -559,114 +542,112 @@ class EvalTrackModel(BaseModel):
             npcs_in["nocs"] = torch.cat([p[2] for p in parts])
             npcs_in["points"], npcs_in["labels"] = input["points"], input["labels"]
             pose = {k: torch.cat([p[3][k] for p in parts]) for k in parts[0][3]}
-            npcs = {k: torch.cat([p[4][k] for p in parts]) for k in parts[0][4]}
-            if replace:
-                npcs_pred[i], pred_poses[i] = npcs, pose
-            else:
-                npcs_pred.append(npcs)
-                pred_poses.append(pose)
-            return pose
+            return {k: torch.cat([p[4][k] for p in parts]) for k in parts[0][4]}, pose
 
-        bounds = [OTF_FIRST_BOUND * N if defer_ok else None] * len(slices)
-        pending = None                  # (frame, poses that entered it, its deferred checks)
-        for i in range(1, len(feed)):
-            frame_nums.append([p.split(".")[-2].split("/")[-1] for p in feed[i]["meta"]["path"]])
-            if pending is not None:
-                pi, pin, checks = pending
-                pending = None
-                verdicts = [c.read() for c in checks if c is not None]
-                if any(r for r, _ in verdicts):
-                    # a rare-path instance in the previous frame: that frame once more, both lanes, on the synchronous stage
-                    parts, done, lane_pose, _ = run_frame(pi, pin, [None] * len(slices))
-                    commit(pi, parts, done, replace=True)
-                elif verdicts:
-                    bounds = [_otf_bound(longest, N) for _, longest in verdicts]
-            consume_noise_draws(feed[i - 1]["gt_part"], self.pose_perturb_cfg)      # (after a replay: see forward())
-            poses_in = lane_pose
-            parts, done, lane_pose, checks = run_frame(i, poses_in, bounds)
-            pose = commit(i, parts, done, replace=False)
-            if any(c is not None for c in checks):
-                pending = (i, poses_in, checks)
-            if self.frame_hook is not None:
-                self.frame_hook(i, pose)
-        if pending is not None:
-            pi, pin, checks = pending
-            if any(c.read()[0] for c in checks if c is not None):
-                parts, done, lane_pose, _ = run_frame(pi, pin, [None] * len(slices))
-                commit(pi, parts, done, replace=True)
-        for st in streams:
-            cur.wait_stream(st)
-        return pred_poses, npcs_pred
+        def join():
+            for st in streams:
+                cur.wait_stream(st)
+
+        first = OTF_FIRST_BOUND * feed[1]["points"].shape[2] if self._otf_defer_usable(feed[1]) else None
+        return run_frame, commit, lane_pose, [first] * len(slices), join
+
+    def _lane_frames(self, pose0):
+        """The frame closures of `forward` for pre-cropped clouds from 32 trajectories on (`_lanes_usable`): graph.TrackLanes hand
+        their poses over themselves, the caller's stream only copies the frame's records out.  Never a deferred check."""
+        feed = self.feed_dict
+        points, mean = feed[1]["points"], feed[1]["points_mean"]
+        had = self._graph
+        lanes = self._cached(("lanes", tuple(points.shape), str(points.device)),
+                             lambda: G.TrackLanes(self, points, mean, pose0, lanes=2, keep_npcs=True))
+        if lanes is had:
+            lanes.set_pose(pose0)          # (a new TrackLanes starts from the pose it was built with)
+
+        def run_frame(i, poses_in, bounds):
+            return lanes.step(feed[i]["points"], feed[i]["points_mean"], sync_inputs=(i == 1)), None, []
+
+        def commit(i, slot):
+            pose, npcs = lanes.gather(slot, npcs=True)
+            return {k: v.clone() for k, v in npcs.items()}, {k: v.clone() for k, v in pose.items()}
+
+        return run_frame, commit, None, [None], None
+
+    def _batch_frames(self, pose0):
+        """The frame closures of `forward` for the whole batch on the caller's stream: re-cropped in place (nocs_otf), then one
+        captured graph or the eager step.  Not a lane: the few-trajectory split-k form stays allowed, and a frame costs no
+        concatenation and no event (the one-trajectory latency would pay for them)."""
+        feed = self.feed_dict
+
+        def run_frame(i, pose_in, bounds):
+            lp = {k: v.clone() for k, v in pose_in.items()}
+            info = self._recrop(i, feed[i], lp, defer=bounds[0]) if self.nocs_otf else None
+            if self._graph_usable(feed[i]):
+                out = self._graph_step(feed[i], lp)
+            else:
+                out = self.track_step(feed[i], self.npcs_feed_dict[i], lp)
+            return out, out[1], ([] if info is None else [_OtfCheck(info)])
+
+        first = OTF_FIRST_BOUND * feed[1]["points"].shape[2] if self._otf_defer_usable(feed[1]) else None
+        return run_frame, (lambda i, out: out), pose0, [first], None
 
     def forward(self, save=False):
-        pred_poses = [self._initial_pose()]
+        """The frame loop.  A batch form hands in `run_frame(i, poses_in, bounds) -> (result, poses_out, checks)`, which enqueues
+        frame i from the poses entering it (bounds[l]: the sync-free re-crop's stride bound of lane l, None = the synchronous
+        stage; checks: the `_OtfCheck` of every sync-free crop), and `commit(i, result) -> (npcs_pred, pose)`, the frame's
+        batch-wide records on the caller's stream."""
+        feed = self.feed_dict
+        pred_poses, npcs_pred = [self._initial_pose()], [None]
         if self.frame_hook is not None:
             self.frame_hook(0, pred_poses[0])
-        npcs_pred = [None]
-        frame_nums = []
         self.timer.tick()
-        lanes = None
-        if len(self.feed_dict) > 1 and self._otf_lanes_usable(self.feed_dict[1]) and self.otf_lanes:
-            frame_nums.append([p.split(".")[-2].split("/")[-1] for p in self.feed_dict[0]["meta"]["path"]])
+        if len(feed) > 1:
+            if self._otf_lanes_usable(feed[1]) and self.otf_lanes:
+                frames = self._otf_lane_frames
+            elif self._lanes_usable(feed[1]):
+                frames = self._lane_frames
+            else:
+                frames = self._batch_frames
             with torch.no_grad():
-                pred_poses, npcs_pred = self._forward_otf_lanes(pred_poses[0], frame_nums)
-            self.pred_dict = {"poses": pred_poses, "npcs_pred": npcs_pred}
-            if save:
-                self._save(frame_nums)
-            return
-        with torch.no_grad():
-            if len(self.feed_dict) > 1 and self._lanes_usable(self.feed_dict[1]):
-                lanes = self._lanes_for(self.feed_dict[1], pred_poses[0])
-            pending, bound = None, OTF_FIRST_BOUND * self.feed_dict[0]["points"].shape[2]
-            for i, input in enumerate(self.feed_dict):
-                frame_nums.append([p.split(".")[-2].split("/")[-1] for p in input["meta"]["path"]])
-                if i == 0:
-                    continue
-                if lanes is not None:
-                    # the lanes hand their poses over themselves; this stream only copies the frame's records out
-                    consume_noise_draws(self.feed_dict[i - 1]["gt_part"], self.pose_perturb_cfg)
-                    pose, cur_npcs = lanes.gather(lanes.step(input["points"], input["points_mean"], sync_inputs=(i == 1)), npcs=True)
-                    npcs_pred.append({k: v.clone() for k, v in cur_npcs.items()})
-                    pred_poses.append({k: v.clone() for k, v in pose.items()})
-                    if self.frame_hook is not None:
-                        self.frame_hook(i, pred_poses[-1])
-                    continue
-                def run(fi, finput, defer):
-                    lp = {k: v.clone() for k, v in pred_poses[fi - 1].items()}
-                    info = self._recrop(fi, finput, lp, defer=defer) if self.nocs_otf else None
-                    if self._graph_usable(finput):
-                        out = self._graph_step(finput, lp)
-                    else:
-                        out = self.track_step(finput, self.npcs_feed_dict[fi], lp)
-                    return out, info
+                run_frame, commit, poses, bounds, join = frames(pred_poses[0])
+                pending = None                  # (frame, poses that entered it, its deferred checks)
 
-                if pending is not None:
-                    # the PREVIOUS frame's deferred verdict: a rare-path instance -> that frame once more, synchronously
-                    rare, longest = pending.read()
-                    pending = None
-                    if rare:
-                        (npcs_pred[i - 1], pred_poses[i - 1]), _ = run(i - 1, self.feed_dict[i - 1], None)
-                    else:
-                        bound = _otf_bound(longest, input["points"].shape[2])
-                # the reference draws (and discards) a perturbed pose every frame (model.py:414); draw it too so that seeded runs
-                # consume the generator identically -- AFTER a replay of the previous frame (its thinning permutations come out of
-                # the same numpy generator and precede this frame's draw in the reference's order)
-                consume_noise_draws(self.feed_dict[i - 1]["gt_part"], self.pose_perturb_cfg)
-                defer = bound if (self.nocs_otf and self._otf_defer_usable(input)) else None
-                (cur_npcs, pose), info = run(i, input, defer)
-                if info is not None:
-                    pending = _OtfCheck(info)
-                npcs_pred.append(cur_npcs)
-                pred_poses.append(pose)
-                if self.frame_hook is not None:
-                    self.frame_hook(i, pose)
-            if pending is not None and pending.read()[0]:
-                last = len(self.feed_dict) - 1
-                (npcs_pred[last], pred_poses[last]), _ = run(last, self.feed_dict[last], None)
+                def settle():
+                    """The pending frame's verdicts, read a frame late: a rare-path instance -> that frame once more on the
+                    synchronous stage, in place of its first run (-> []); else the lanes' longest candidate lists."""
+                    nonlocal pending, poses
+                    if pending is None:
+                        return []
+                    (pi, pin, checks), pending = pending, None
+                    verdicts = [c.read() for c in checks]
+                    if not any(rare for rare, _ in verdicts):
+                        return [longest for _, longest in verdicts]
+                    result, poses, _ = run_frame(pi, pin, [None] * len(bounds))
+                    npcs_pred[pi], pred_poses[pi] = commit(pi, result)
+                    return []
+
+                for i in range(1, len(feed)):
+                    longest = settle()
+                    if longest:
+                        bounds = [_otf_bound(n, feed[i]["points"].shape[2]) for n in longest]
+                    # the reference draws (and discards) a perturbed pose every frame (model.py:414); draw it too so that seeded runs
+                    # consume the generator identically -- AFTER a replay of the previous frame (its thinning permutations come out of
+                    # the same numpy generator and precede this frame's draw in the reference's order)
+                    consume_noise_draws(feed[i - 1]["gt_part"], self.pose_perturb_cfg)
+                    poses_in = poses
+                    result, poses, checks = run_frame(i, poses_in, bounds)
+                    npcs, pose = commit(i, result)
+                    npcs_pred.append(npcs)
+                    pred_poses.append(pose)
+                    if checks:
+                        pending = (i, poses_in, checks)
+                    if self.frame_hook is not None:
+                        self.frame_hook(i, pose)
+                settle()
+                if join is not None:
+                    join()
         self.pred_dict = {"poses": pred_poses, "npcs_pred": npcs_pred}
         self.check_l1_stream()
         if save:
-            self._save(frame_nums)
+            self._save(list(map(_frame_names, feed)))
 
     def _save(self, frame_nums):
         """Per-trajectory pickle {'pred': {'poses','corners'}, 'gt': {'poses','corners'}, 'frame_nums'}

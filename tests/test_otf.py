@@ -96,7 +96,7 @@ def test_track_loop_with_on_the_fly_crop(device):
 @pytest.mark.gpu
 @pytest.mark.parametrize("hipgraph", [False, True])
 def test_track_loop_otf_lanes_equal_single_batch(device, hipgraph):
-    """nocs_otf at 32 trajectories: the two lanes half a frame apart (EvalTrackModel._forward_otf_lanes: one lane re-crops and
+    """nocs_otf at 32 trajectories: the two lanes half a frame apart (EvalTrackModel._otf_lane_frames: one lane re-crops and
     samples while the other runs its networks) give the SAME poses, CoordinateNet maps and re-cropped clouds as the whole
     batch processed in one piece -- bit for bit, eager and with captured steps; the loss dict (IoUs included) agrees."""
     from captra_amd.configs import make_config

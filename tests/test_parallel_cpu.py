@@ -282,3 +282,47 @@ def test_scale_tool_dry_run_lists_the_north_star_table():
     cats = [r["category"] for r in mix["ranks"]]
     assert cats == [str(1 + r % 6) for r in range(8)] and set(cats) == {"1", "2", "3", "4", "5", "6"}
     assert "--nproc-per-node=8" in by["configs[4] backbone16k x8"]["command"]
+
+
+def test_frame_loop_replays_a_rare_frame_before_the_next_noise_draw(monkeypatch, tmp_path):
+    """The deferred re-crop protocol of EvalTrackModel.forward on the host, driven by recording stand-ins for a batch form's
+    closures: a frame's verdict is read one frame late; a rare verdict runs that frame again with every bound None, in place of
+    its first run, BEFORE the next frame's discarded noise draw and without touching the bounds; any other verdict sets the
+    next bounds; the last frame's verdict is read (and the frame run again) after the loop."""
+    import captra_amd.model as M
+    from captra_amd.configs import make_config
+    from captra_amd.synthetic import make_trajectory
+    cfg = make_config("1", experiment_dir=str(tmp_path), **{"init_frame/gt": True})
+    cfg["device"] = "cpu"
+    log, rare_frames = [], {2, 3}
+
+    class Check:
+        def __init__(self, i):
+            self.i = i
+
+        def read(self):
+            log.append(("read", self.i))
+            return self.i in rare_frames, 100 * self.i
+
+    class RecordingModel(M.EvalTrackModel):
+        def _batch_frames(self, pose0):
+            def run_frame(i, pose_in, bounds):
+                log.append(("run", i, tuple(bounds)))
+                return (i, tuple(bounds)), pose_in, [] if bounds[0] is None else [Check(i)]
+
+            def commit(i, result):
+                log.append(("commit", i))
+                return {"ran": result}, pose0
+            return run_frame, commit, pose0, [7], None
+
+    monkeypatch.setattr(M, "consume_noise_draws", lambda part, perturb: log.append(("draw",)))
+    monkeypatch.setattr(M, "_otf_bound", lambda longest, n: longest + 1)
+    model = RecordingModel(cfg).eval()
+    model.set_data(make_trajectory("nocs", 2, 4, seed=0))
+    model.forward()
+    assert log == [("draw",), ("run", 1, (7,)), ("commit", 1),
+                   ("read", 1), ("draw",), ("run", 2, (101,)), ("commit", 2),
+                   ("read", 2), ("run", 2, (None,)), ("commit", 2), ("draw",), ("run", 3, (101,)), ("commit", 3),
+                   ("read", 3), ("run", 3, (None,)), ("commit", 3)]
+    assert [n and n["ran"] for n in model.pred_dict["npcs_pred"]] == [None, (1, (7,)), (2, (None,)), (3, (None,))]
+    assert len(model.pred_dict["poses"]) == 4
