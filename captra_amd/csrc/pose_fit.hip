@@ -218,6 +218,11 @@ __device__ void jacobi_eig3(double A[9], double V[9]) {
 
 // R = [u1 u2 u1xu2][v1 v2 v1xv2]^T with v1,v2 the leading eigenvectors of M^T M, u_i = M v_i/|M v_i|:
 // equals U diag(1,1,det(UV^T)) V^T for either sign of det(M) (see oracle/captra_oracle.c).
+// Rank <= 1 (collinear or coincident points, one point, no point): M v2 (and for M = 0 also M v1) is zero, u2 = M v2/|M v2|
+// would be 0/0 -- u is completed with an arbitrary orthonormal vector instead, the identity for M = 0.  sigma_2 counts as zero
+// below KABSCH_RANK1_REL * sigma_1: there M v2 holds nothing but the rounding of the double arithmetic (~1e-16 sigma_1), and
+// a sigma_2 that small moves the objective tr(R^T M) by 1e-12 sigma_1, four orders below the fp32 rounding of R.
+constexpr double KABSCH_RANK1_REL = 1e-12;
 __device__ void kabsch3(const double M[9], double R[9]) {
     double A[9], V[9];
     for (int i = 0; i < 3; ++i)
@@ -247,12 +252,24 @@ __device__ void kabsch3(const double M[9], double R[9]) {
         n1 += u1[i] * u1[i];
         n2 += u2[i] * u2[i];
     }
-    n1 = sqrt(n1);
-    n2 = sqrt(n2);
+    n1 = sqrt(n1);  // sigma_1
+    n2 = sqrt(n2);  // sigma_2
+    if (n1 == 0.0) {  // M = 0: every rotation is optimal -- the identity
+        for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+        return;
+    }
     double dp = 0;
-    for (int i = 0; i < 3; ++i) {
-        u1[i] /= n1;
-        u2[i] /= n2;
+    for (int i = 0; i < 3; ++i) u1[i] /= n1;
+    if (n2 <= KABSCH_RANK1_REL * n1) {
+        // rank 1: M v2 is zero or rounding noise, and every unit vector orthogonal to u1 completes an optimal rotation
+        // (tr(R^T M) = sigma_1 for all of them) -- take the coordinate axis farthest from u1; the Gram-Schmidt step below
+        // makes it orthonormal (|e_k - u1_k u1|^2 = 1 - u1_k^2 >= 2/3)
+        int k = 0;
+        if (fabs(u1[1]) < fabs(u1[k])) k = 1;
+        if (fabs(u1[2]) < fabs(u1[k])) k = 2;
+        for (int i = 0; i < 3; ++i) u2[i] = (i == k) ? 1.0 : 0.0;
+    } else {
+        for (int i = 0; i < 3; ++i) u2[i] /= n2;
     }
     for (int i = 0; i < 3; ++i) dp += u1[i] * u2[i];
     double nn = 0;

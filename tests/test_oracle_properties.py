@@ -1,9 +1,11 @@
 """Property tests of the CPU oracle (hypothesis): the invariants the reference's algorithms guarantee by construction, on
 random small clouds -- independent of the golden vectors, so that an oracle bug cannot hide behind a matching fixture."""
 import numpy as np
+import pytest
 from hypothesis import given, settings, strategies as st
 
 from oracle import ops as O
+from tests import test_pose_readout_gpu as PR          # the Procrustes case builders and float64 reference (numpy only)
 
 clouds_st = st.integers(0, 2 ** 31 - 1).flatmap(lambda seed: st.tuples(st.just(seed), st.integers(5, 200), st.integers(1, 40)))
 
@@ -83,3 +85,17 @@ def test_pointwise_mlp_is_the_fmaf_chain(seed, cin, cout, length):
     bound = 4e-7 * (np.abs(b)[:, None] + np.abs(w.T) @ np.abs(x[0])) * max(cin, 1) ** 0.5 + 1e-30
     assert (np.abs(y - ref) <= bound).all()
     assert (y >= 0).all()
+
+
+# ---- 3x3 Procrustes: the sweep and the degenerate cases of tests/test_pose_readout_gpu.py on the oracle -----------------------
+# The oracle's kabsch3 is the kernel's restated, so an oracle-against-kernel comparison cannot see a flaw both share; these hold
+# the oracle itself to the float64 SVD (finite, orthonormal, det = +1, optimal tr(R^T M); the matrix where it is unique).
+@pytest.mark.parametrize("n", PR.SWEEP_N)
+def test_procrustes_rot3_conditioning_sweep(n):
+    PR.check_sweep(n, lambda src, tgt: O.procrustes_rot3(src[None], tgt[None])[0])
+
+
+@pytest.mark.parametrize("name", [c[0] for c in PR.degenerate_cases()])
+def test_procrustes_rot3_degenerate(name):
+    (src, tgt), = [c[1:] for c in PR.degenerate_cases() if c[0] == name]
+    PR.check_rotation(O.procrustes_rot3(src[None], tgt[None])[0], src, tgt, name, compare_matrix=False)
