@@ -17,6 +17,7 @@ segmentation, NOCS and box-IoU figures (loss.py, bbox_utils.py).
 from __future__ import annotations
 
 import contextlib
+import logging
 import pickle
 from copy import deepcopy
 from os.path import join as pjoin
@@ -107,6 +108,11 @@ def _frame_names(frame):
     return [p.split(".")[-2].split("/")[-1] for p in frame["meta"]["path"]]
 
 
+# init_frame/fit: the inlier distance of the first-pose fit as a fraction of data_radius -- 3 mm at the NOCS crops' 0.6 m: the
+# reference's preprocessing uses 1 mm on rendered (exact) maps (align_pose.py:49), sensor depth at 1 m is noisy at the millimetre
+INIT_FIT_INLIER_TH = 0.005
+
+
 class EvalTrackModel(BaseModel):
     def __init__(self, cfg):
         super().__init__(cfg)
@@ -115,6 +121,13 @@ class EvalTrackModel(BaseModel):
         self.tree = cfg["obj_tree"]
         self.root = [p for p in range(len(self.tree)) if self.tree[p] == -1][0]
         self.gt_init = cfg["init_frame"]["gt"]
+        # init_frame: {fit: True}: the first pose is FITTED to frame 0's own NOCS map, labels and points (RANSAC similarity fit,
+        # csrc/pose_ransac.hip) -- no pose annotation is needed to start a track.  inlier_th is a fraction of data_radius (default
+        # INIT_FIT_INLIER_TH); num_hyps hypotheses drawn in the kernel from `seed`.  Absent / False: nothing changes.
+        self.fit_init = bool(cfg["init_frame"].get("fit", False))
+        self.fit_init_cfg = {"inlier_th": float(cfg["init_frame"].get("inlier_th", INIT_FIT_INLIER_TH)) * float(cfg["data_radius"]),
+                             "num_hyps": int(cfg["init_frame"].get("num_hyps", 64)), "seed": int(cfg["init_frame"].get("seed", 0))}
+        self._fit_fallback_logged = False
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
         self.radius = cfg["data_radius"]
         self.track_cfg = cfg["track_cfg"]
@@ -201,6 +214,10 @@ class EvalTrackModel(BaseModel):
 
     # ---- the loop ------------------------------------------------------------------------------
     def _initial_pose(self):
+        part = self._annotated_initial_pose()
+        return self._fitted_initial_pose(part) if self.fit_init else part
+
+    def _annotated_initial_pose(self):
         gt_part = self.feed_dict[0]["gt_part"]
         if self.gt_init:
             return gt_part
@@ -210,6 +227,29 @@ class EvalTrackModel(BaseModel):
                                             self.num_parts, self.device)
             part["translation"], part["scale"] = crop["translation"], crop["scale"]
         return part
+
+    def _fitted_initial_pose(self, fallback):
+        """init_frame/fit: all B x P first poses from frame 0's NOCS map (B,3,N), labels (B,N) and points (B,3,N) + points_mean in
+        one launch; a part whose fit is invalid (fewer than three members or inliers) keeps `fallback`."""
+        from .pose_utils.pose_fit import part_fit_ransac_cn
+        first = self.feed_dict[0]
+        missing = [k for k in ("nocs", "labels", "points") if k not in first]
+        if missing:
+            raise KeyError(f"init_frame/fit needs frame 0's {missing} (NOCS map, instance labels, points)")
+        nocs = first["nocs"].float()
+        B, P, N = nocs.shape[0], self.num_parts, nocs.shape[-1]
+        src = (nocs if nocs.dim() == 4 else nocs.unsqueeze(1).expand(B, P, 3, N)).contiguous()
+        mean = first["meta"]["points_mean"].float().to(self.device)
+        rot, scale, trans, valid, _ = part_fit_ransac_cn(first["labels"].int().contiguous(), src, first["points"].float().contiguous(),
+                                                         num_hyps=self.fit_init_cfg["num_hyps"], inlier_th=self.fit_init_cfg["inlier_th"],
+                                                         seed=self.fit_init_cfg["seed"], target_mean=mean)
+        if not self._fit_fallback_logged and not bool(valid.all()):
+            self._fit_fallback_logged = True
+            logging.getLogger(__name__).warning("init_frame/fit: %d of %d first-pose fits are invalid; those parts start from the "
+                                                "annotated pose", int((~valid).sum()), valid.numel())
+        return {"rotation": torch.where(valid[..., None, None], rot, fallback["rotation"]),
+                "scale": torch.where(valid, scale, fallback["scale"]),
+                "translation": torch.where(valid[..., None, None], trans, fallback["translation"])}
 
     @contextlib.contextmanager
     def _step_context(self, points, allow_split_k=True):

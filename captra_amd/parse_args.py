@@ -21,7 +21,7 @@ _FLAGS = [  # (name, type, default)
     ("num_workers", int, 0), ("dataset_length", int, None), ("pointnet_cfg/camera", str, None),
     ("network/type", str, None), ("network/nocs_head_dims", int, None), ("network/backbone_out_dim", int, None),
     ("network/pwm_num", int, None),
-    ("init_frame/gt", boolean_string, None), ("nocs_otf", boolean_string, None),
+    ("init_frame/gt", boolean_string, None), ("init_frame/fit", boolean_string, None), ("nocs_otf", boolean_string, None),
     ("track_cfg/gt_label", boolean_string, None), ("track_cfg/nocs2d_label", boolean_string, None), ("track_cfg/nocs2d_path", str, None),
     # optimisation
     ("total_epoch", int, None), ("optimizer", str, None), ("weight_decay", float, None), ("learning_rate", float, None),

@@ -1,8 +1,11 @@
-"""Per-part scale/translation fit from NOCS <-> camera correspondences, one HIP launch.
+"""Per-part pose fits from NOCS <-> camera correspondences, one HIP launch each.
 
 Mirrors `part_fit_st_no_ransac` / `filter_model_valid` of the reference's pose_utils/pose_fit.py
 (l.26-53).  The reference builds a one-hot mask and runs transform_pts_mask (~30 ATen kernels and
 a host SVD for symmetric objects); here the labels go straight to captra_part_fit_st.
+
+`part_fit_ransac` is the estimator that needs no previous pose: the RANSAC similarity fit `pose_fit` of the reference's
+datasets/nocs_data/preproc_nocs/align_pose.py:49-93 (host numpy there), captra_part_fit_ransac here.
 """
 from __future__ import annotations
 
@@ -63,3 +66,47 @@ def part_fit_st_no_ransac(labels, source, target, rotation, cfg, given_scale=Non
                                                given_scale=gs, tgt_per_part=True)
     model = {"rotation": rotation, "scale": scale, "translation": translation}
     return model, filter_model_valid(model, valid)
+
+
+def part_fit_ransac_cn(labels_i32, src_cn, tgt_cn, num_hyps=64, inlier_th=1e-3, sample_rank=None, seed=0, target_mean=None,
+                       tgt_per_part=False, want_samples=False):
+    """Channel-major form (no transposes): labels (B,N) int32, src_cn (B,P,3,N), tgt_cn (B,3,N) [or (B,P,3,N) with
+    tgt_per_part], target_mean (B,3[,1]) or None (the target is tgt + mean, one fp32 addition in the kernel), sample_rank
+    (B,P,H,3) int32 member ranks or None (drawn in the kernel from `seed`, include/captra_hip.h)
+    -> rotation (B,P,3,3), scale (B,P), translation (B,P,3,1), valid (B,P) bool, info {'best', 'num_inliers' (B,P) int32
+    [, 'samples' (B,P,H,3) int32 point indices]}.  An invalid fit is identity / 1 / 0."""
+    B, P, _, N = src_cn.shape
+    dev = src_cn.device
+    if target_mean is not None:
+        target_mean = target_mean.reshape(B, 3).float().contiguous()
+    if sample_rank is not None:
+        sample_rank = sample_rank.reshape(B, P, num_hyps, 3).int().contiguous()
+    L.require_device(labels_i32, src_cn, tgt_cn, target_mean, sample_rank)
+    rot = torch.empty(B, P, 3, 3, dtype=torch.float32, device=dev)
+    scale = torch.empty(B, P, dtype=torch.float32, device=dev)
+    trans = torch.empty(B, P, 3, dtype=torch.float32, device=dev)
+    valid = torch.empty(B, P, dtype=torch.int32, device=dev)
+    best = torch.empty(B, P, dtype=torch.int32, device=dev)
+    ninl = torch.empty(B, P, dtype=torch.int32, device=dev)
+    samples = torch.empty(B, P, num_hyps, 3, dtype=torch.int32, device=dev) if want_samples else None
+    with torch.cuda.device(dev):
+        L.call("captra_part_fit_ransac", B, P, N, int(num_hyps), float(inlier_th), L.ptr(labels_i32), L.ptr(src_cn), L.ptr(tgt_cn),
+               1 if tgt_per_part else 0, L.ptr(target_mean), L.ptr(sample_rank), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(rot), L.ptr(scale),
+               L.ptr(trans), L.ptr(valid), L.ptr(best), L.ptr(ninl), L.ptr(samples))
+    info = {"best": best, "num_inliers": ninl}
+    if want_samples:
+        info["samples"] = samples
+    return rot, scale, trans.unsqueeze(-1), valid.bool(), info
+
+
+def part_fit_ransac(labels, source, target, cfg, num_hyps=64, inlier_th=1e-3, sample_rank=None, seed=0, target_mean=None):
+    """The reference layouts of part_fit_st_no_ransac: labels (B,N); source (B,P,N,3); target (B,P,N,3) or (B,N,3);
+    cfg {'num_parts'} -> ({'rotation' (B,P,3,3), 'scale' (B,P), 'translation' (B,P,3,1)}, valid (B,P) bool,
+    info {'best', 'num_inliers'})."""
+    assert source.shape[1] == int(cfg["num_parts"]), (source.shape, cfg["num_parts"])
+    src_cn = source.transpose(-1, -2).float().contiguous()
+    tgt_cn = target.transpose(-1, -2).float().contiguous()
+    rot, scale, trans, valid, info = part_fit_ransac_cn(labels.int().contiguous(), src_cn, tgt_cn, num_hyps=num_hyps, inlier_th=inlier_th,
+                                                        sample_rank=sample_rank, seed=seed, target_mean=target_mean,
+                                                        tgt_per_part=target.dim() == 4)
+    return {"rotation": rot, "scale": scale, "translation": trans}, valid, info

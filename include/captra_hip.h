@@ -615,6 +615,35 @@ int captra_part_fit_st_track(int b, int p, int n, int sym, const int *labels, co
                              const float *pts_mean, const float *rot, const float *prev_scale, const float *prev_trans,
                              float *scale, float *trans, int *valid, captra_stream_t stream);
 
+/* RANSAC similarity fit (rotation + scale + translation) of NOCS coordinates to camera points for all (trajectory, part) pairs in
+ * one launch: pose_fit of the reference's datasets/nocs_data/preproc_nocs/align_pose.py:49-93, the estimator that needs no previous
+ * pose.  One workgroup per (b, p); 1 <= P <= 8, 1 <= num_hyps <= 256, 1 <= N <= 16384, anything else returns -1 without a launch.
+ *   labels (B,N) i32 (values outside [0,P) belong to no part); src = NOCS (B,P,3,N) channel-major; tgt = camera points, (B,3,N)
+ *   shared by the parts (tgt_per_part = 0) or (B,P,3,N) (tgt_per_part = 1); tgt_mean (B,3) or NULL: the target is tgt + mean, ONE
+ *   fp32 addition, as in captra_part_fit_st_track.  Points that are not members of the part may hold NaN / Inf: they are never read
+ *   into an output.
+ *   members  = the points with label p in ascending point index, `count` of them; rank r (>= 0) = the (r mod count)-th member.
+ *   sampling : sample_rank (B,P,H,3) i32 gives the three ranks of hypothesis h as they are (duplicates make a degenerate
+ *              hypothesis that scores what it scores).  NULL: three DISTINCT ranks from a counter-based integer generator,
+ *                mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)   (mod 2^64)
+ *                key = mix(seed + 0x9E3779B97F4A7C15);  u(d) = mix(key ^ (b << 32 | p << 24 | h << 8 | d)) >> 32         (32 bits)
+ *                r0 = u(0) mod count;  r1 = u(1) mod (count - 1), +1 if r1 >= r0;
+ *                r2 = u(2) mod (count - 2), +1 if r2 >= min(r0, r1), then +1 if r2 >= max(r0, r1)
+ *              -- integer arithmetic only, a pure function of (seed, b, p, h, d, count).
+ *   hypothesis (Umeyama on the three pairs, in double): centre both; R = U diag(1, 1, det(U V^T)) V^T of tgt_c^T src_c;
+ *              s = sum (R src_c).tgt_c / (sum |R src_c|^2 + 1e-6); t = mean(tgt - s R src).  (s R, t) are rounded to fp32.
+ *   score(h) = #{members: |tgt - (s R src + t)|^2 < inlier_th^2}, each operation a separately rounded fp32 one; a NaN residual is
+ *              outside.  best = the FIRST h with the largest score (numpy argmax).
+ *   refit    : the same Umeyama on the inliers of best, sums in double.
+ *   -> rot (B,P,3,3), scale (B,P), trans (B,P,3), valid (B,P) i32 = count >= 3 && inliers >= 3 && every output finite; an invalid
+ *      fit writes identity / 1 / 0 (no NaN leaves the kernel).  Optional (NULL = not wanted): best (B,P) i32, num_inliers (B,P) i32
+ *      (what was found, also for an invalid fit), samples_out (B,P,H,3) i32 the POINT indices of the three members used.  With
+ *      count < 3 nothing is drawn or scored: best = 0, num_inliers = 0, samples_out = -1. */
+int captra_part_fit_ransac(int b, int p, int n, int num_hyps, float inlier_th, const int *labels, const float *src, const float *tgt,
+                           int tgt_per_part, const float *tgt_mean, const int *sample_rank, unsigned long long seed, float *rot,
+                           float *scale, float *trans, int *valid, int *best, int *num_inliers, int *samples_out,
+                           captra_stream_t stream);
+
 /* CoordinateNet read-out (networks.py:50 F.softmax(dim=1) + model.py:466 torch.max(seg, dim=-2)[1]) in one launch: logits (B,S,N),
  * S <= 8 -> seg (B,S,N) softmax (or NULL), labels (B,N) i32 = FIRST index of the largest logit (or NULL). */
 int captra_seg_softmax_argmax(int b, int s, int n, const float *logits, float *seg, int *labels, captra_stream_t stream);
