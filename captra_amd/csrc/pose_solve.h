@@ -1,8 +1,24 @@
-// The 3x3 orthogonal Procrustes solve shared by pose_fit.hip (captra_procrustes_rot3) and pose_ransac.hip (captra_part_fit_ransac):
-// double-precision cyclic Jacobi on M^T M, and the rotation U diag(1,1,det(UV^T)) V^T read off its eigenvectors.
+// The 3x3 orthogonal Procrustes solve shared by pose_fit.hip (captra_procrustes_rot3) and the RANSAC fit (pose_ransac.h:
+// captra_part_fit_ransac, captra_part_fit_guard): double-precision cyclic Jacobi on M^T M, and the rotation
+// U diag(1,1,det(UV^T)) V^T read off its eigenvectors.  And the ONE inlier test of the RANSAC fit and the track guard.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+// |t - (sR s + tr)|^2 under the twelve parameters hp = (sR row-major, tr), every operation a separately rounded fp32 one
+static __device__ __forceinline__ float rs_residual2(const float s[3], const float t[3], const float hp[12]) {
+    float e[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float pr = ((hp[a * 3] * s[0] + hp[a * 3 + 1] * s[1]) + hp[a * 3 + 2] * s[2]) + hp[9 + a];
+        e[a] = t[a] - pr;
+    }
+    return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+}
+// ... < th2; a NaN residual is no inlier
+static __device__ __forceinline__ bool rs_inlier(const float s[3], const float t[3], const float hp[12], float th2) {
+    return rs_residual2(s, t, hp) < th2;
+}
 
 static __device__ void jacobi_eig3(double A[9], double V[9]) {
     for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;

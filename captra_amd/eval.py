@@ -74,6 +74,21 @@ def eval_data(name: str, data: dict, obj_info: dict, device=None) -> dict:
     return errors
 
 
+def guard_table(name: str, data: dict) -> list:
+    """The track guard's record of one result pickle (present when the run had track_cfg/guard): one line per part with the frames
+    whose verdict was lost / recovered / too_few."""
+    from .pose_utils.pose_fit import GUARD_VERDICTS
+    frames = [(i, np.asarray(g["verdict"]).reshape(-1)) for i, g in enumerate(data["guard"]) if g is not None]
+    lines = []
+    for p in range(len(frames[0][1]) if frames else 0):
+        cols = []
+        for code in (2, 3, 1):
+            hit = [str(i) for i, v in frames if int(v[p]) == code]
+            cols.append(f"{GUARD_VERDICTS[code]} {len(hit)}" + (f" [{' '.join(hit)}]" if hit else ""))
+        lines.append(f"{name} part {p}: " + "; ".join(cols) + f" (of {len(frames)} frames)")
+    return lines
+
+
 def write_csv(errors: dict, path: str) -> None:
     keys = list(next(iter(errors.values())).keys())
     with open(path, "w") as f:
@@ -99,10 +114,13 @@ def main(argv=None) -> dict:
     del args.eval_device
     cfg = get_config(args, save=False)
     data_path = pjoin(cfg["experiment_dir"], "results", "data")
-    errors = {}
+    errors, guard_lines = {}, []
     for raw in sorted(os.listdir(data_path)):
         with open(pjoin(data_path, raw), "rb") as f:
-            errors.update(eval_data(raw.rsplit(".", 1)[0], pickle.load(f), cfg["obj_info"], device))
+            data = pickle.load(f)
+        errors.update(eval_data(raw.rsplit(".", 1)[0], data, cfg["obj_info"], device))
+        if "guard" in data:
+            guard_lines += guard_table(raw.rsplit(".", 1)[0], data)
     if not errors:
         raise SystemExit(f"no result pickles under {data_path}")
     err_path = pjoin(cfg["experiment_dir"], "results", "err.pkl")
@@ -112,6 +130,10 @@ def main(argv=None) -> dict:
     avg = {k: float(np.mean([row[k] for row in errors.values()])) for k in next(iter(errors.values()))}
     for k, v in avg.items():
         print(f"{k}: {v}")
+    if guard_lines:
+        print("track guard, frames per trajectory and part:")
+        for line in guard_lines:
+            print("  " + line)
     return avg
 
 

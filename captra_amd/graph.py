@@ -43,9 +43,12 @@ def lane_streams(dev, lanes: int = 2):
     return have[:lanes]
 
 
-def step_inputs(points, points_mean, labels=None):
-    """The (input, npcs_input) dict pair EvalTrackModel.track_step takes, over one cloud."""
+def step_inputs(points, points_mean, labels=None, b0: int = 0):
+    """The (input, npcs_input) dict pair EvalTrackModel.track_step takes, over one cloud (b0: the index of its first trajectory
+    within the whole batch, for a lane of one)."""
     input = {"points": points, "points_mean": points_mean, "meta": {}}
+    if b0:
+        input["b0"] = int(b0)
     npcs_input = {"points": points, "points_mean": points_mean}
     if labels is not None:
         input["labels"] = npcs_input["labels"] = labels
@@ -54,7 +57,7 @@ def step_inputs(points, points_mean, labels=None):
 
 class TrackStepGraph:
     def __init__(self, model, points: torch.Tensor, points_mean: torch.Tensor, pose: dict, labels: torch.Tensor | None = None,
-                 warmup: int = 2, split_side=None, allow_split_k: bool = True):
+                 warmup: int = 2, split_side=None, allow_split_k: bool = True, b0: int = 0):
         """model: EvalTrackModel (eval mode, on the GPU); points (B,3,N), points_mean (B,3,1), pose: example inputs.
         split_side: a stream -> the step is captured as four linear graphs and its RotationNet branch replays on that stream
         (see SPLIT_OTF_LANES); None -> one graph, the networks as its two branches when model.overlap_nets."""
@@ -63,6 +66,7 @@ class TrackStepGraph:
         # a LANE of a larger batch (TrackLanes) must compute what the whole batch computes: the few-trajectory split-k rule of
         # EvalTrackModel._step_context goes by the batch it sees, so it is switched off for sub-batches
         self.allow_split_k = allow_split_k
+        self.b0 = int(b0)          # a lane's first trajectory within the whole batch: the track guard draws by it (a launch argument, captured)
         dev = points.device
         self.points = points.clone()
         self.points_mean = points_mean.clone()
@@ -104,7 +108,7 @@ class TrackStepGraph:
         """[prep] -> [rot || coord] -> [post] as four linear graphs.  RotationNet's graph allocates from a pool of its own: it
         replays beside CoordinateNet's, so memory one of them frees while being captured must not be handed to the other."""
         m = self.model
-        inp, npcs_in = step_inputs(self.points, self.points_mean, self.labels)
+        inp, npcs_in = step_inputs(self.points, self.points_mean, self.labels, b0=self.b0)
         if not m._overlap_nets(inp):
             return False
         cap = torch.cuda.Stream(device=self.points.device)
@@ -151,7 +155,7 @@ class TrackStepGraph:
         g_post.replay()
 
     def _step(self):
-        return self.model.track_step(*step_inputs(self.points, self.points_mean, self.labels), self.pose, allow_split_k=self.allow_split_k)
+        return self.model.track_step(*step_inputs(self.points, self.points_mean, self.labels, b0=self.b0), self.pose, allow_split_k=self.allow_split_k)
 
     def stale(self) -> bool:
         """True when a module UNDER THIS GRAPH'S MODEL re-folded (or dropped) its weights after the capture: the replay would
@@ -216,7 +220,8 @@ class TrackLanes:
         dev = points.device
         per = B // lanes
         self.slices = [slice(l * per, (l + 1) * per) for l in range(lanes)]
-        self.graphs = [TrackStepGraph(model, points[s].contiguous(), points_mean[s].contiguous(), {k: v[s].contiguous() for k, v in pose.items()}, allow_split_k=False)
+        self.graphs = [TrackStepGraph(model, points[s].contiguous(), points_mean[s].contiguous(), {k: v[s].contiguous() for k, v in pose.items()}, allow_split_k=False,
+                                      b0=s.start)
                        for s in self.slices]
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(lanes)]
         self.ring = [{k: torch.empty_like(v) for k, v in pose.items()} for _ in range(ring)]
@@ -261,7 +266,7 @@ class TrackLanes:
                 pairs = [(out[k], self.ring[slot][k][s]) for k in out] + [(out[k], g.pose[k]) for k in out]
                 if self.npcs_ring is not None:
                     pairs += [(g.npcs_pred[k], dst[s]) for k, dst in self.npcs_ring[slot].items()]
-                fused.copy_multi(pairs)
+                fused.copy_multi(pairs)                  # (6 pose + 3 map jobs, 4 more with a guard record: within the launch's 16)
                 self.written[slot][l].record(st)
         return slot
 

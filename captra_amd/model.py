@@ -111,6 +111,7 @@ def _frame_names(frame):
 # init_frame/fit: the inlier distance of the first-pose fit as a fraction of data_radius -- 3 mm at the NOCS crops' 0.6 m: the
 # reference's preprocessing uses 1 mm on rendered (exact) maps (align_pose.py:49), sensor depth at 1 m is noisy at the millimetre
 INIT_FIT_INLIER_TH = 0.005
+GUARD_KEYS = ("count", "inliers", "rms", "verdict")     # a frame's guard record: (B,P) tensors (pose_utils/pose_fit.py)
 
 
 class EvalTrackModel(BaseModel):
@@ -128,6 +129,10 @@ class EvalTrackModel(BaseModel):
         self.fit_init_cfg = {"inlier_th": float(cfg["init_frame"].get("inlier_th", INIT_FIT_INLIER_TH)) * float(cfg["data_radius"]),
                              "num_hyps": int(cfg["init_frame"].get("num_hyps", 64)), "seed": int(cfg["init_frame"].get("seed", 0))}
         self._fit_fallback_logged = False
+        # track_cfg: {guard: {...}}: every step checks the pose it produced against the frame's own NOCS map, labels and points
+        # (csrc/pose_guard.hip, one launch behind the pose fit, captured with the step) and, with refit, re-fits a part found lost
+        # by the first-pose estimator.  Absent: no launch, no tensor, no pickle entry.
+        self.guard = self._guard_cfg(cfg)
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
         self.radius = cfg["data_radius"]
         self.track_cfg = cfg["track_cfg"]
@@ -170,6 +175,20 @@ class EvalTrackModel(BaseModel):
         self.otf_lanes = bool(cfg.get("otf_lanes", True))
         self._graph = None
         self._graph_key = None
+
+    @staticmethod
+    def _guard_cfg(cfg):
+        g = cfg["track_cfg"].get("guard")
+        if g is None:
+            return None
+        if g.get("lost_below") is None:
+            raise ValueError("track_cfg/guard needs lost_below (the inlier fraction below which a part counts as lost): it has no default")
+        from .pose_utils.pose_fit import lost_ratio
+        # lost_below as the two ints the kernel compares with, converted once (raises on a value outside [0, 1])
+        return {"refit": bool(g.get("refit", False)), "lost_below": lost_ratio(g["lost_below"]),
+                "inlier_th": float(g.get("inlier_th", INIT_FIT_INLIER_TH)) * float(cfg["data_radius"]),
+                "min_members": int(g.get("min_members", 4)), "num_hyps": int(g.get("num_hyps", cfg["init_frame"].get("num_hyps", 64))),
+                "seed": int(g.get("seed", cfg["init_frame"].get("seed", 0)))}
 
     # ---- host -> device ------------------------------------------------------------------------
     def _gt_part(self, frame):
@@ -262,7 +281,8 @@ class EvalTrackModel(BaseModel):
                 yield
 
     def track_step(self, input, npcs_input, last_pose, allow_split_k=True):
-        """One frame for all B trajectories: CoordNet -> labels -> RotationNet -> pose fit."""
+        """One frame for all B trajectories: CoordNet -> labels -> RotationNet -> pose fit [-> guard].  input['b0']: the index
+        of the first trajectory within the whole batch when `input` is a lane of one (the guard's draws; default 0)."""
         with self._step_context(input["points"], allow_split_k):
             self._step_begin(input, npcs_input, last_pose)
             join = self._fork_rotation_net(input, npcs_input, last_pose) if self._overlap_nets(input) else None
@@ -370,7 +390,24 @@ class EvalTrackModel(BaseModel):
         input.pop("shared_geometry", None)
         if self.share_geometry and self.num_parts == 1 and not self.npcs_net.training:
             input["shared_geometry"] = (self.npcs_net.last_canon, self.npcs_net.backbone.last_geom)
-        return self.net(input, test_mode=True)["part"]
+        pose = self.net(input, test_mode=True)["part"]
+        return pose if self.guard is None else self._guard_step(input, npcs_pred, pose)
+
+    def _guard_step(self, input, npcs_pred, pose):
+        """The guard behind the pose fit, on the labels the fit used; its record joins CoordinateNet's maps (`guard_*`), so it
+        travels with them through every batch form; -> the step's pose (the re-fit where a lost part was recovered)."""
+        from .pose_utils.pose_fit import part_fit_guard_cn
+        g = self.guard
+        labels = input.get("pred_labels_i32")
+        if labels is None:
+            labels = input["pred_labels"].int().contiguous()
+        pose, info = part_fit_guard_cn(labels, input["pred_nocs"].float().contiguous(), input["points"].float().contiguous(),
+                                       input["points_mean"], pose, inlier_th=g["inlier_th"], lost_below=g["lost_below"],
+                                       min_members=g["min_members"], refit=g["refit"], num_hyps=g["num_hyps"], seed=g["seed"],
+                                       b0=int(input.get("b0", 0)))
+        for k in GUARD_KEYS:
+            npcs_pred["guard_" + k] = info[k]
+        return pose
 
     # ---- the two networks side by side -------------------------------------------------------------------------------
     def _overlap_nets(self, input) -> bool:
@@ -430,7 +467,7 @@ class EvalTrackModel(BaseModel):
         """One frame through the captured graph (captured on first use for this batch shape); outputs are cloned out
         of the graph's static buffers."""
         points, mean = input["points"], input["points_mean"]
-        graph = self._cached((tuple(points.shape), str(points.device)), lambda: G.TrackStepGraph(self, points, mean, last_pose))
+        graph = self._cached((tuple(points.shape), str(points.device)), lambda: G.TrackStepGraph(self, points, mean, last_pose))   # (the whole batch: b0 = 0)
         return graph.replay_cloned(points, mean, last_pose)
 
     def _lanes_usable(self, input) -> bool:
@@ -525,7 +562,7 @@ class EvalTrackModel(BaseModel):
         if self._graph_usable(feed[1]):
             graphs = self._cached(("otf", tuple(feed[1]["points"].shape), str(dev)), lambda: [
                 G.TrackStepGraph(self, feed[1]["points"][s].contiguous(), feed[1]["points_mean"][s].contiguous(),
-                                 {k: v[s].contiguous() for k, v in pose0.items()}, split_side=side, allow_split_k=False) for s, side in zip(slices, sides)])
+                                 {k: v[s].contiguous() for k, v in pose0.items()}, split_side=side, allow_split_k=False, b0=s.start) for s, side in zip(slices, sides)])
         lane_pose = [{k: v[s].clone() for k, v in pose0.items()} for s in slices]
         for st in streams:
             st.wait_stream(cur)
@@ -556,7 +593,7 @@ class EvalTrackModel(BaseModel):
                     if graphs is not None:
                         cur_npcs, pose = graphs[l].replay_cloned(pts, mean, poses_in[l])
                     else:
-                        cur_npcs, pose = self.track_step(*G.step_inputs(pts, mean, labels), poses_in[l])
+                        cur_npcs, pose = self.track_step(*G.step_inputs(pts, mean, labels, b0=s.start), poses_in[l])
                         cur_npcs = {k: v for k, v in cur_npcs.items() if torch.is_tensor(v)}
                     poses_out.append(pose)
                     ev = torch.cuda.Event()
@@ -636,6 +673,7 @@ class EvalTrackModel(BaseModel):
         batch-wide records on the caller's stream."""
         feed = self.feed_dict
         pred_poses, npcs_pred = [self._initial_pose()], [None]
+        guard = {}                          # frame -> its guard record (guard on)
         if self.frame_hook is not None:
             self.frame_hook(0, pred_poses[0])
         self.timer.tick()
@@ -648,6 +686,8 @@ class EvalTrackModel(BaseModel):
                 frames = self._batch_frames
             with torch.no_grad():
                 run_frame, commit, poses, bounds, join = frames(pred_poses[0])
+                if self.guard is not None:
+                    commit = self._commit_with_guard(commit, guard)
                 pending = None                  # (frame, poses that entered it, its deferred checks)
 
                 def settle():
@@ -685,9 +725,20 @@ class EvalTrackModel(BaseModel):
                 if join is not None:
                     join()
         self.pred_dict = {"poses": pred_poses, "npcs_pred": npcs_pred}
+        if self.guard is not None:
+            self.pred_dict["guard"] = [None] + [guard[i] for i in range(1, len(feed))]
         self.check_l1_stream()
         if save:
             self._save(list(map(_frame_names, feed)))
+
+    @staticmethod
+    def _commit_with_guard(commit, records):
+        """`commit` of a batch form, with the frame's guard record taken out of CoordinateNet's maps into records[frame]."""
+        def wrapped(i, result):
+            npcs, pose = commit(i, result)
+            records[i] = {k: npcs.pop("guard_" + k) for k in GUARD_KEYS}
+            return npcs, pose
+        return wrapped
 
     def _save(self, frame_nums):
         """Per-trajectory pickle {'pred': {'poses','corners'}, 'gt': {'poses','corners'}, 'frame_nums'}
@@ -714,6 +765,8 @@ class EvalTrackModel(BaseModel):
         save_dict = {"pred": {"poses": [to_np(p) for p in self.pred_dict["poses"]], "corners": corner_list},
                      "gt": {"poses": [to_np(f["gt_part"]) for f in self.feed_dict], "corners": gt_corners},
                      "frame_nums": frame_nums}
+        if self.guard is not None:
+            save_dict["guard"] = [None if g is None else {k: v.detach().cpu().numpy() for k, v in g.items()} for g in self.pred_dict["guard"]]
         records = []
         for i, path in enumerate(self.feed_dict[0]["meta"]["path"]):
             instance, track_num = path.split(".")[-2].split("/")[-3:-1]

@@ -23,6 +23,9 @@ _FLAGS = [  # (name, type, default)
     ("network/pwm_num", int, None),
     ("init_frame/gt", boolean_string, None), ("init_frame/fit", boolean_string, None), ("nocs_otf", boolean_string, None),
     ("track_cfg/gt_label", boolean_string, None), ("track_cfg/nocs2d_label", boolean_string, None), ("track_cfg/nocs2d_path", str, None),
+    # track health (model.py: EvalTrackModel.guard); lost_below has no default
+    ("track_cfg/guard/refit", boolean_string, None), ("track_cfg/guard/lost_below", float, None), ("track_cfg/guard/inlier_th", float, None),
+    ("track_cfg/guard/min_members", int, None), ("track_cfg/guard/num_hyps", int, None), ("track_cfg/guard/seed", int, None),
     # optimisation
     ("total_epoch", int, None), ("optimizer", str, None), ("weight_decay", float, None), ("learning_rate", float, None),
     ("lr_policy", str, None), ("lr_gamma", float, None), ("lr_step_size", int, None), ("lr_clip", float, None), ("freq/save", int, None),

@@ -110,3 +110,53 @@ def part_fit_ransac(labels, source, target, cfg, num_hyps=64, inlier_th=1e-3, sa
                                                         sample_rank=sample_rank, seed=seed, target_mean=target_mean,
                                                         tgt_per_part=target.dim() == 4)
     return {"rotation": rot, "scale": scale, "translation": trans}, valid, info
+
+
+GUARD_VERDICTS = ("ok", "too_few", "lost", "recovered")      # the codes 0..3 of captra_part_fit_guard
+
+
+def lost_ratio(lost_below) -> tuple[int, int]:
+    """The fraction `lost_below` as the two ints (L, D) the guard compares with (inliers * D < L * count): the fraction the number
+    was WRITTEN as (0.3 -> 3/10, not the binary float next to it), denominators up to 2^20; a pair (L, D) passes through."""
+    from fractions import Fraction
+    if isinstance(lost_below, (tuple, list)):
+        num, den = int(lost_below[0]), int(lost_below[1])
+    else:
+        f = Fraction(repr(float(lost_below))).limit_denominator(1 << 20)
+        num, den = f.numerator, f.denominator
+    if num < 0 or den < 1 or num > den:
+        raise ValueError(f"lost_below must be a fraction in [0, 1], got {lost_below!r}")
+    return num, den
+
+
+def part_fit_guard_cn(labels_i32, src_cn, pts_cn, pts_mean, pose, inlier_th, lost_below, min_members=4, refit=False, num_hyps=64,
+                      seed=0, b0=0):
+    """Track health in one launch (captra_part_fit_guard, include/captra_hip.h): labels (B,N) int32, src_cn (B,P,3,N) predicted
+    NOCS, pts_cn (B,3,N), pts_mean (B,3[,1]) or None, pose {'rotation' (B,P,3,3), 'scale' (B,P), 'translation' (B,P,3,1)} = the
+    step's pose; lost_below a fraction (see lost_ratio); b0 = the index of the first trajectory within the whole batch.
+    -> (pose dict, info {'count', 'inliers' (B,P) int32, 'rms' (B,P) float32, 'verdict' (B,P) int32: GUARD_VERDICTS}).
+    refit=False: the pose dict IS `pose` (nothing is written); refit=True: new tensors, the re-fit where verdict == 3 and the input
+    bits everywhere else."""
+    B, P, _, N = src_cn.shape
+    dev = src_cn.device
+    num, den = lost_ratio(lost_below)
+    if pts_mean is not None:
+        pts_mean = pts_mean.reshape(B, 3).float().contiguous()
+    rot = pose["rotation"].float().contiguous()
+    scale = pose["scale"].float().contiguous()
+    trans = pose["translation"].reshape(B, P, 3).float().contiguous()
+    L.require_device(labels_i32, src_cn, pts_cn, pts_mean, rot, scale, trans)
+    count = torch.empty(B, P, dtype=torch.int32, device=dev)
+    inliers = torch.empty(B, P, dtype=torch.int32, device=dev)
+    rms = torch.empty(B, P, dtype=torch.float32, device=dev)
+    verdict = torch.empty(B, P, dtype=torch.int32, device=dev)
+    out = (torch.empty_like(rot), torch.empty_like(scale), torch.empty_like(trans)) if refit else (None, None, None)
+    with torch.cuda.device(dev):
+        L.call("captra_part_fit_guard", B, P, N, int(b0), L.ptr(labels_i32), L.ptr(src_cn), L.ptr(pts_cn), L.ptr(pts_mean), L.ptr(rot),
+               L.ptr(scale), L.ptr(trans), float(inlier_th), num, den, int(min_members), 1 if refit else 0, int(num_hyps),
+               int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(count), L.ptr(inliers), L.ptr(rms), L.ptr(verdict), L.ptr(out[0]), L.ptr(out[1]),
+               L.ptr(out[2]))
+    info = {"count": count, "inliers": inliers, "rms": rms, "verdict": verdict}
+    if not refit:
+        return pose, info
+    return {"rotation": out[0], "scale": out[1], "translation": out[2].unsqueeze(-1)}, info

@@ -644,6 +644,35 @@ int captra_part_fit_ransac(int b, int p, int n, int num_hyps, float inlier_th, c
                            float *scale, float *trans, int *valid, int *best, int *num_inliers, int *samples_out,
                            captra_stream_t stream);
 
+/* Track health (no reference counterpart: its loop runs open loop after frame 0): per (trajectory, part) a check of the step's pose
+ * against the frame's own correspondences and, for a part found lost, a re-fit by captra_part_fit_ransac's estimator -- one launch,
+ * one workgroup per (b, p), same shape limits as captra_part_fit_ransac (anything else, b0 < 0, lost_den < 1, lost_num < 0,
+ * refit outside {0, 1} or refit = 1 with a NULL pose output returns -1 without a launch).
+ *   labels (B,N) i32 (values outside [0,P) belong to no part); src = predicted NOCS (B,P,3,N); pts (B,3,N), pts_mean (B,3) or NULL:
+ *   the target is pts + mean, ONE fp32 addition; the step's pose rot (B,P,3,3), scale (B,P), trans (B,P,3).
+ *   check    : over the members of (b, p), the inlier test of captra_part_fit_ransac under the twelve parameters
+ *              (fp32(scale * rot[i][j]), trans): |tgt - (sR src + t)|^2 < inlier_th^2, every operation a separately rounded fp32
+ *              one, a NaN residual is no inlier.  -> count (B,P) i32 members, inliers (B,P) i32, rms (B,P) f32 = sqrt of the mean of
+ *              the inliers' squared residuals (the fp32 values, summed in double in a fixed order; 0 without inliers).
+ *   verdict  (B,P) i32: 1 too_few  = count < min_members (never re-fitted);
+ *                       2 lost     = inliers * lost_den < lost_num * count (integers: the fraction lost_num / lost_den is exact);
+ *                       0 ok       otherwise;
+ *                       3 recovered (refit = 1 only), below.
+ *   re-fit   : refit = 1 and the part is lost: captra_part_fit_ransac on the same members (tgt_per_part = 0, sample_rank = NULL,
+ *              num_hyps, inlier_th, seed) with b0 + b in place of b in the draw key -- b0 = the index of this launch's first
+ *              trajectory in the whole batch, so that a lane of a batch draws what the whole batch draws.  Accepted when that fit
+ *              is valid and its best hypothesis scores STRICTLY more inliers than the tracked pose had: verdict 3 and
+ *              rot_out / scale_out / trans_out are that fit's outputs, bit for bit.  In every other case the pose outputs are the
+ *              input pose, bit for bit.  With refit = 0 the pose outputs may be NULL.  Outputs must not alias inputs.
+ * A workgroup whose part is not lost leaves after the check.  No NaN is produced: rms is finite, a re-fit is finite or rejected.
+ * PRECONDITION for "no NaN leaves the kernel": the input pose is finite -- the pass-through copies it bit for bit, a non-finite one
+ * included (its part then has no inliers and counts as lost).  In the track step the pose comes from captra_part_fit_st_track,
+ * which keeps the previous scale / translation where a fit is not finite.  refit = 0 asks for the member list's LDS only. */
+int captra_part_fit_guard(int b, int p, int n, int b0, const int *labels, const float *src, const float *pts, const float *pts_mean,
+                          const float *rot, const float *scale, const float *trans, float inlier_th, int lost_num, int lost_den,
+                          int min_members, int refit, int num_hyps, unsigned long long seed, int *count, int *inliers, float *rms,
+                          int *verdict, float *rot_out, float *scale_out, float *trans_out, captra_stream_t stream);
+
 /* CoordinateNet read-out (networks.py:50 F.softmax(dim=1) + model.py:466 torch.max(seg, dim=-2)[1]) in one launch: logits (B,S,N),
  * S <= 8 -> seg (B,S,N) softmax (or NULL), labels (B,N) i32 = FIRST index of the largest logit (or NULL). */
 int captra_seg_softmax_argmax(int b, int s, int n, const float *logits, float *seg, int *labels, captra_stream_t stream);
