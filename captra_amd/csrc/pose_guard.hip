@@ -13,6 +13,8 @@
 //   4. only for a lost part with refit = 1: the coordinates into LDS and the RANSAC fit's own stages (pose_ransac.h, the same
 //      device functions as captra_part_fit_ransac: same members, same draws with b0 + b in the key, same bits); accepted when it
 //      is valid and its best hypothesis scores strictly more inliers than the tracked pose had.
+// captra_part_fit_guard_sym is the same kernel instantiated with the axis-only test of the symmetric categories (pose_solve.h:
+// RsTest<true>): step 2 forms the seven parameters (second column of rot, scale, trans), and the re-fit scores by the same test.
 // Everything a verdict depends on is uniform over the workgroup (block-wide integer sums), so whole workgroups leave after 3.
 #include "pose_ransac.h"
 
@@ -20,6 +22,7 @@ namespace {
 
 enum { GUARD_OK = 0, GUARD_TOO_FEW = 1, GUARD_LOST = 2, GUARD_RECOVERED = 3 };
 
+template <bool SYM>
 __global__ __launch_bounds__(RS_THREADS) void part_fit_guard_kernel(int p, int n, int b0, const int *__restrict__ labels,
                                                                     const float *__restrict__ src, const float *__restrict__ pts,
                                                                     const float *__restrict__ pts_mean, const float *__restrict__ rot,
@@ -53,12 +56,21 @@ __global__ __launch_bounds__(RS_THREADS) void part_fit_guard_kernel(int p, int n
     const int count = rs_list_members(labels + (size_t)bi * n, pi, n, idx, lds.wcnt);
 
     // ---- 2. the tracked pose against them
+    using Test = RsTest<SYM>;
     const float sc = scale[q];
-    float hp[12];
+    float hp[Test::NPAR];
+    if constexpr (SYM) {        // (a, scale, trans): the y-axis as the pose holds it, taken as a unit vector
 #pragma unroll
-    for (int i = 0; i < 9; ++i) hp[i] = sc * rot[(size_t)q * 9 + i];
+        for (int a = 0; a < 3; ++a) hp[a] = rot[(size_t)q * 9 + a * 3 + 1];
+        hp[3] = sc;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) hp[9 + a] = trans[(size_t)q * 3 + a];
+        for (int a = 0; a < 3; ++a) hp[4 + a] = trans[(size_t)q * 3 + a];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) hp[i] = sc * rot[(size_t)q * 9 + i];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) hp[9 + a] = trans[(size_t)q * 3 + a];
+    }
     const float th2 = th * th;
     int mine = 0;
     double sq[1] = {0.0};
@@ -69,8 +81,9 @@ __global__ __launch_bounds__(RS_THREADS) void part_fit_guard_kernel(int p, int n
         if (m < count) {
             float s[3], t[3];
             mem.load(m, s, t);
-            e2 = rs_residual2(s, t, hp);
-            in = rs_inlier(s, t, hp, th2);
+            const float rho = SYM ? rs_sym_radius(s) : 0.f;
+            e2 = Test::residual2(s, rho, t, hp);
+            in = Test::inlier(s, rho, t, hp, th2);
         }
         mine += __popcll(__ballot(in));
         if (in) sq[0] += (double)e2;
@@ -90,7 +103,7 @@ __global__ __launch_bounds__(RS_THREADS) void part_fit_guard_kernel(int p, int n
     RsResult res;
     if (refit && verdict == GUARD_LOST) {       // (uniform)
         rs_stage_members(mem, count, co);
-        rs_fit(mem, count, q, b0 + bi, pi, num_hyps, th, nullptr, seed, nullptr, lds, res);
+        rs_fit<SYM>(mem, count, q, b0 + bi, pi, num_hyps, th, nullptr, seed, nullptr, lds, res);
     }
 
     if (tid == 0) {
@@ -109,20 +122,39 @@ __global__ __launch_bounds__(RS_THREADS) void part_fit_guard_kernel(int p, int n
 
 }  // namespace
 
-extern "C" int captra_part_fit_guard(int b, int p, int n, int b0, const int *labels, const float *src, const float *pts,
-                                     const float *pts_mean, const float *rot, const float *scale, const float *trans, float inlier_th,
-                                     int lost_num, int lost_den, int min_members, int refit, int num_hyps, unsigned long long seed,
-                                     int *count, int *inliers, float *rms, int *verdict, float *rot_out, float *scale_out,
-                                     float *trans_out, captra_stream_t stream) {
+template <bool SYM>
+static int part_fit_guard_launch(int b, int p, int n, int b0, const int *labels, const float *src, const float *pts, const float *pts_mean,
+                                 const float *rot, const float *scale, const float *trans, float inlier_th, int lost_num, int lost_den,
+                                 int min_members, int refit, int num_hyps, unsigned long long seed, int *count, int *inliers, float *rms,
+                                 int *verdict, float *rot_out, float *scale_out, float *trans_out, captra_stream_t stream) {
     if (b < 0 || p < 1 || p > RS_MAX_P || n < 1 || n > RS_MAX_N || num_hyps < 1 || num_hyps > RS_MAX_H) return -1;
     if (b0 < 0 || b0 > 0x7fffffff - b || lost_num < 0 || lost_den < 1 || (refit != 0 && refit != 1)) return -1;
     if (refit && (rot_out == nullptr || scale_out == nullptr || trans_out == nullptr)) return -1;
     if (b == 0) return 0;
     // (monitoring touches the member list alone: it asks for that much LDS and no more, so that workgroups share a CU)
-    constexpr auto kern = part_fit_guard_kernel;
+    constexpr auto kern = part_fit_guard_kernel<SYM>;
     if (int e = captra_allow_lds<kern>(RS_LDS_MAX)) return e;
-    CAPTRA_LAUNCH("part_fit_guard", kern, dim3(b * p), dim3(RS_THREADS), refit ? rs_lds_bytes(n) : rs_idx_bytes(n), (hipStream_t)stream, p, n, b0, labels, src, pts,
-                  pts_mean, rot, scale, trans, inlier_th, lost_num, lost_den, min_members, refit, num_hyps, seed, count, inliers, rms,
-                  verdict, rot_out, scale_out, trans_out);
+    CAPTRA_LAUNCH(SYM ? "part_fit_guard_sym" : "part_fit_guard", kern, dim3(b * p), dim3(RS_THREADS), refit ? rs_lds_bytes(n) : rs_idx_bytes(n),
+                  (hipStream_t)stream, p, n, b0, labels, src, pts, pts_mean, rot, scale, trans, inlier_th, lost_num, lost_den, min_members, refit,
+                  num_hyps, seed, count, inliers, rms, verdict, rot_out, scale_out, trans_out);
     return captra_last_error();
+}
+
+extern "C" int captra_part_fit_guard(int b, int p, int n, int b0, const int *labels, const float *src, const float *pts,
+                                     const float *pts_mean, const float *rot, const float *scale, const float *trans, float inlier_th,
+                                     int lost_num, int lost_den, int min_members, int refit, int num_hyps, unsigned long long seed,
+                                     int *count, int *inliers, float *rms, int *verdict, float *rot_out, float *scale_out,
+                                     float *trans_out, captra_stream_t stream) {
+    return part_fit_guard_launch<false>(b, p, n, b0, labels, src, pts, pts_mean, rot, scale, trans, inlier_th, lost_num, lost_den, min_members,
+                                        refit, num_hyps, seed, count, inliers, rms, verdict, rot_out, scale_out, trans_out, stream);
+}
+
+// the axis-only inlier test of the symmetric categories in the check AND in the re-fit: both counts of the acceptance rule by one test
+extern "C" int captra_part_fit_guard_sym(int b, int p, int n, int b0, const int *labels, const float *src, const float *pts,
+                                         const float *pts_mean, const float *rot, const float *scale, const float *trans, float inlier_th,
+                                         int lost_num, int lost_den, int min_members, int refit, int num_hyps, unsigned long long seed,
+                                         int *count, int *inliers, float *rms, int *verdict, float *rot_out, float *scale_out,
+                                         float *trans_out, captra_stream_t stream) {
+    return part_fit_guard_launch<true>(b, p, n, b0, labels, src, pts, pts_mean, rot, scale, trans, inlier_th, lost_num, lost_den, min_members,
+                                       refit, num_hyps, seed, count, inliers, rms, verdict, rot_out, scale_out, trans_out, stream);
 }

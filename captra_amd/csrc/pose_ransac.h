@@ -170,7 +170,10 @@ struct RsResult {
 
 // Stages 2-4 of the fit on the `count` listed members of part (bi, pi); q = the part's index in this launch (sample_rank /
 // samples_out rows), key_b = the trajectory's index in the draw key.  Every thread of the workgroup calls it (barriers inside);
-// with count < 3 nothing is drawn or scored.
+// with count < 3 nothing is drawn or scored.  SYM: a hypothesis is scored, and the winner's inliers are selected, by the axis-only
+// test (pose_solve.h) on (fp32 second column of R_h, fp32 s_h, fp32 t_h) -- seven floats in the same twelve-float slot; draws,
+// hypotheses, work items, first best, the refit and the validity rule are the same code.
+template <bool SYM>
 __device__ __forceinline__ void rs_fit(const RsMembers &mem, int count, int q, int key_b, int pi, int num_hyps, float th,
                                        const int *__restrict__ sample_rank, unsigned long long seed, int *__restrict__ samples_out,
                                        RsLds &L, RsResult &res) {
@@ -226,33 +229,41 @@ __device__ __forceinline__ void rs_fit(const RsMembers &mem, int count, int q, i
             }
             double R[9], sca, tr[3];
             rs_umeyama(M, C6, sb, tb, R, &sca, tr);
-            for (int i = 0; i < 9; ++i) L.hp[h * 12 + i] = (float)(sca * R[i]);
-            for (int a = 0; a < 3; ++a) L.hp[h * 12 + 9 + a] = (float)tr[a];
+            if constexpr (SYM) {
+                for (int a = 0; a < 3; ++a) L.hp[h * 12 + a] = (float)R[a * 3 + 1];
+                L.hp[h * 12 + 3] = (float)sca;
+                for (int a = 0; a < 3; ++a) L.hp[h * 12 + 4 + a] = (float)tr[a];
+            } else {
+                for (int i = 0; i < 9; ++i) L.hp[h * 12 + i] = (float)(sca * R[i]);
+                for (int a = 0; a < 3; ++a) L.hp[h * 12 + 9 + a] = (float)tr[a];
+            }
         }
         __syncthreads();
 
         // ---- 3. scores
+        using Test = RsTest<SYM>;
         const float th2 = th * th;
         const int chunks = (count + RS_CHUNK - 1) / RS_CHUNK, groups = (num_hyps + RS_HG - 1) / RS_HG;
         for (int item = wave; item < chunks * groups; item += RS_WAVES) {
             const int c = item / groups, g = item % groups;
-            float s[RS_PPL][3], t[RS_PPL][3];
+            float s[RS_PPL][3], t[RS_PPL][3], rho[RS_PPL];
             bool have[RS_PPL];
 #pragma unroll
             for (int k = 0; k < RS_PPL; ++k) {
                 const int m = c * RS_CHUNK + k * 64 + lane;
                 have[k] = m < count;
                 mem.load(have[k] ? m : 0, s[k], t[k]);
+                rho[k] = SYM ? rs_sym_radius(s[k]) : 0.f;       // (once per member, not per hypothesis)
             }
             int mine = 0;
             const int h1 = (g + 1) * RS_HG < num_hyps ? (g + 1) * RS_HG : num_hyps;
             for (int h = g * RS_HG; h < h1; ++h) {
-                float hp[12];
+                float hp[Test::NPAR];
 #pragma unroll
-                for (int i = 0; i < 12; ++i) hp[i] = L.hp[h * 12 + i];
+                for (int i = 0; i < Test::NPAR; ++i) hp[i] = L.hp[h * 12 + i];
                 int pc = 0;
 #pragma unroll
-                for (int k = 0; k < RS_PPL; ++k) pc += __popcll(__ballot(have[k] && rs_inlier(s[k], t[k], hp, th2)));
+                for (int k = 0; k < RS_PPL; ++k) pc += __popcll(__ballot(have[k] && Test::inlier(s[k], rho[k], t[k], hp, th2)));
                 mine = (lane == h - g * RS_HG) ? pc : mine;
             }
             if (g * RS_HG + lane < h1) atomicAdd(&L.score[g * RS_HG + lane], mine);
@@ -276,16 +287,16 @@ __device__ __forceinline__ void rs_fit(const RsMembers &mem, int count, int q, i
         __syncthreads();
         res.best = L.best;
         res.ninl = L.score[res.best];
-        float hp[12];
+        float hp[Test::NPAR];
 #pragma unroll
-        for (int i = 0; i < 12; ++i) hp[i] = L.hp[res.best * 12 + i];
+        for (int i = 0; i < Test::NPAR; ++i) hp[i] = L.hp[res.best * 12 + i];
 
         if (res.ninl >= 3) {    // (uniform)
             double r1[7] = {0, 0, 0, 0, 0, 0, 0};
             for (int m = tid; m < count; m += RS_THREADS) {
                 float s[3], t[3];
                 mem.load(m, s, t);
-                if (rs_inlier(s, t, hp, th2)) {
+                if (Test::inlier(s, SYM ? rs_sym_radius(s) : 0.f, t, hp, th2)) {
                     r1[0] += 1.0;
 #pragma unroll
                     for (int a = 0; a < 3; ++a) {
@@ -303,7 +314,7 @@ __device__ __forceinline__ void rs_fit(const RsMembers &mem, int count, int q, i
             for (int m = tid; m < count; m += RS_THREADS) {
                 float s[3], t[3];
                 mem.load(m, s, t);
-                if (rs_inlier(s, t, hp, th2)) {
+                if (Test::inlier(s, SYM ? rs_sym_radius(s) : 0.f, t, hp, th2)) {
                     double sc[3], tc[3];
 #pragma unroll
                     for (int a = 0; a < 3; ++a) {

@@ -16,11 +16,14 @@
 //   4. best = first h with the largest score; two double block reductions over its inliers (count and centroids, then the
 //      centred cross-covariance and source covariance) and one thread finishes the same Umeyama solve.
 // The inlier test is one fp32 expression of (member, hypothesis) alone, evaluated by the same inline function in 3. and 4.:
-// the inlier set is a pure function of the inputs, whatever the wave that meets the member.
+// the inlier set is a pure function of the inputs, whatever the wave that meets the member.  captra_part_fit_ransac_sym is the
+// same kernel instantiated with the axis-only test of the symmetric categories (pose_solve.h: RsTest<true>), whose per-hypothesis
+// parameters are (second column of R, s, t); the output rotation is still the full Kabsch rotation of the refit.
 #include "pose_ransac.h"
 
 namespace {
 
+template <bool SYM>
 __global__ __launch_bounds__(RS_THREADS) void part_fit_ransac_kernel(int p, int n, int num_hyps, float th, int tgt_per_part,
                                                                      const int *__restrict__ labels, const float *__restrict__ src,
                                                                      const float *__restrict__ tgt, const float *__restrict__ tgt_mean,
@@ -49,7 +52,7 @@ __global__ __launch_bounds__(RS_THREADS) void part_fit_ransac_kernel(int p, int 
     const int count = rs_list_members(labels + (size_t)bi * n, pi, n, idx, lds.wcnt);      // 1. (pose_ransac.h)
     rs_stage_members(mem, count, co);
     RsResult res;
-    rs_fit(mem, count, q, bi, pi, num_hyps, th, sample_rank, seed, samples_out, lds, res);  // 2.-4.
+    rs_fit<SYM>(mem, count, q, bi, pi, num_hyps, th, sample_rank, seed, samples_out, lds, res);  // 2.-4.
 
     if (threadIdx.x == 0) {
         for (int i = 0; i < 9; ++i) rot[(size_t)q * 9 + i] = res.R[i];
@@ -63,16 +66,34 @@ __global__ __launch_bounds__(RS_THREADS) void part_fit_ransac_kernel(int p, int 
 
 }  // namespace
 
+template <bool SYM>
+static int part_fit_ransac_launch(int b, int p, int n, int num_hyps, float inlier_th, const int *labels, const float *src, const float *tgt,
+                                  int tgt_per_part, const float *tgt_mean, const int *sample_rank, unsigned long long seed, float *rot,
+                                  float *scale, float *trans, int *valid, int *best, int *num_inliers, int *samples_out,
+                                  captra_stream_t stream) {
+    if (b < 0 || p < 1 || p > RS_MAX_P || n < 1 || n > RS_MAX_N || num_hyps < 1 || num_hyps > RS_MAX_H) return -1;
+    if (b == 0) return 0;
+    constexpr auto kern = part_fit_ransac_kernel<SYM>;
+    if (int e = captra_allow_lds<kern>(RS_LDS_MAX)) return e;
+    CAPTRA_LAUNCH(SYM ? "part_fit_ransac_sym" : "part_fit_ransac", kern, dim3(b * p), dim3(RS_THREADS), rs_lds_bytes(n), (hipStream_t)stream,
+                  p, n, num_hyps, inlier_th, tgt_per_part, labels, src, tgt, tgt_mean, sample_rank, seed, rot, scale, trans, valid, best,
+                  num_inliers, samples_out);
+    return captra_last_error();
+}
+
 extern "C" int captra_part_fit_ransac(int b, int p, int n, int num_hyps, float inlier_th, const int *labels, const float *src,
                                       const float *tgt, int tgt_per_part, const float *tgt_mean, const int *sample_rank,
                                       unsigned long long seed, float *rot, float *scale, float *trans, int *valid, int *best,
                                       int *num_inliers, int *samples_out, captra_stream_t stream) {
-    if (b < 0 || p < 1 || p > RS_MAX_P || n < 1 || n > RS_MAX_N || num_hyps < 1 || num_hyps > RS_MAX_H) return -1;
-    if (b == 0) return 0;
-    constexpr auto kern = part_fit_ransac_kernel;
-    if (int e = captra_allow_lds<kern>(RS_LDS_MAX)) return e;
-    CAPTRA_LAUNCH("part_fit_ransac", kern, dim3(b * p), dim3(RS_THREADS), rs_lds_bytes(n), (hipStream_t)stream, p, n, num_hyps,
-                  inlier_th, tgt_per_part, labels, src, tgt, tgt_mean, sample_rank, seed, rot, scale, trans, valid, best, num_inliers,
-                  samples_out);
-    return captra_last_error();
+    return part_fit_ransac_launch<false>(b, p, n, num_hyps, inlier_th, labels, src, tgt, tgt_per_part, tgt_mean, sample_rank, seed, rot,
+                                         scale, trans, valid, best, num_inliers, samples_out, stream);
+}
+
+// the axis-only inlier test of the symmetric categories in the scores and in the winner's inlier set; everything else as above
+extern "C" int captra_part_fit_ransac_sym(int b, int p, int n, int num_hyps, float inlier_th, const int *labels, const float *src,
+                                          const float *tgt, int tgt_per_part, const float *tgt_mean, const int *sample_rank,
+                                          unsigned long long seed, float *rot, float *scale, float *trans, int *valid, int *best,
+                                          int *num_inliers, int *samples_out, captra_stream_t stream) {
+    return part_fit_ransac_launch<true>(b, p, n, num_hyps, inlier_th, labels, src, tgt, tgt_per_part, tgt_mean, sample_rank, seed, rot,
+                                        scale, trans, valid, best, num_inliers, samples_out, stream);
 }

@@ -20,6 +20,35 @@ static __device__ __forceinline__ bool rs_inlier(const float s[3], const float t
     return rs_residual2(s, t, hp) < th2;
 }
 
+// The AXIS-ONLY test of the symmetric categories (include/captra_hip.h, captra_part_fit_guard_sym): the camera point lies where the
+// NOCS point's height and radius put it on the surface of revolution about the pose's y-axis; no in-plane angle enters.  Seven
+// parameters ap = (a = second column of rot, scale, trans); rho = rs_sym_radius(s) depends on the member alone, so a caller that
+// meets a member under many poses forms it once.  w = d - h a and not |d|^2 - h^2: the latter cancels near the axis.
+static __device__ __forceinline__ float rs_sym_radius(const float s[3]) { return sqrtf(s[0] * s[0] + s[2] * s[2]); }
+static __device__ __forceinline__ float rs_residual2_sym(float sy, float rho, const float t[3], const float ap[7]) {
+    const float d0 = t[0] - ap[4], d1 = t[1] - ap[5], d2 = t[2] - ap[6];
+    const float h = (ap[0] * d0 + ap[1] * d1) + ap[2] * d2;
+    const float w0 = d0 - h * ap[0], w1 = d1 - h * ap[1], w2 = d2 - h * ap[2];
+    const float rt = sqrtf((w0 * w0 + w1 * w1) + w2 * w2);
+    const float eh = h - ap[3] * sy, er = rt - ap[3] * rho;
+    return eh * eh + er * er;
+}
+
+// The test a kernel instantiated with SYM applies, and how many of a hypothesis's twelve-float slot it reads: the full-rotation
+// test on (sR, t), or the axis-only one on (a, scale, t).  rho is read with SYM alone.
+template <bool SYM>
+struct RsTest {
+    static constexpr int NPAR = SYM ? 7 : 12;
+    static __device__ __forceinline__ float residual2(const float s[3], float rho, const float t[3], const float *hp) {
+        if constexpr (SYM) return rs_residual2_sym(s[1], rho, t, hp);
+        else return rs_residual2(s, t, hp);
+    }
+    static __device__ __forceinline__ bool inlier(const float s[3], float rho, const float t[3], const float *hp, float th2) {
+        if constexpr (SYM) return rs_residual2_sym(s[1], rho, t, hp) < th2;      // (a NaN residual is no inlier)
+        else return rs_inlier(s, t, hp, th2);
+    }
+};
+
 static __device__ void jacobi_eig3(double A[9], double V[9]) {
     for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
     for (int sweep = 0; sweep < 30; ++sweep) {

@@ -78,7 +78,7 @@ def guard_table(name: str, data: dict) -> list:
     """The track guard's record of one result pickle (present when the run had track_cfg/guard): one line per part with the frames
     whose verdict was lost / recovered / too_few."""
     from .pose_utils.pose_fit import GUARD_VERDICTS
-    frames = [(i, np.asarray(g["verdict"]).reshape(-1)) for i, g in enumerate(data["guard"]) if g is not None]
+    frames = [(i, np.asarray(g["verdict"]).reshape(-1)) for i, g in enumerate(data["guard"]) if g is not None and "verdict" in g]
     lines = []
     for p in range(len(frames[0][1]) if frames else 0):
         cols = []
@@ -87,6 +87,12 @@ def guard_table(name: str, data: dict) -> list:
             cols.append(f"{GUARD_VERDICTS[code]} {len(hit)}" + (f" [{' '.join(hit)}]" if hit else ""))
         lines.append(f"{name} part {p}: " + "; ".join(cols) + f" (of {len(frames)} frames)")
     return lines
+
+
+def guard_test_name(data: dict) -> str:
+    """Which inlier test the run's guard used: the boolean a run with track_cfg/guard/yaxis_only carries in the slot of frame 0."""
+    head = data["guard"][0] if data["guard"] else None
+    return "axis-only" if head is not None and bool(np.all(head.get("yaxis_only", False))) else "full-rotation"
 
 
 def write_csv(errors: dict, path: str) -> None:
@@ -114,13 +120,14 @@ def main(argv=None) -> dict:
     del args.eval_device
     cfg = get_config(args, save=False)
     data_path = pjoin(cfg["experiment_dir"], "results", "data")
-    errors, guard_lines = {}, []
+    errors, guard_lines, guard_tests = {}, [], set()
     for raw in sorted(os.listdir(data_path)):
         with open(pjoin(data_path, raw), "rb") as f:
             data = pickle.load(f)
         errors.update(eval_data(raw.rsplit(".", 1)[0], data, cfg["obj_info"], device))
         if "guard" in data:
             guard_lines += guard_table(raw.rsplit(".", 1)[0], data)
+            guard_tests.add(guard_test_name(data))
     if not errors:
         raise SystemExit(f"no result pickles under {data_path}")
     err_path = pjoin(cfg["experiment_dir"], "results", "err.pkl")
@@ -131,7 +138,7 @@ def main(argv=None) -> dict:
     for k, v in avg.items():
         print(f"{k}: {v}")
     if guard_lines:
-        print("track guard, frames per trajectory and part:")
+        print(f"track guard ({' / '.join(sorted(guard_tests))} inlier test), frames per trajectory and part:")
         for line in guard_lines:
             print("  " + line)
     return avg

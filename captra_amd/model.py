@@ -128,11 +128,16 @@ class EvalTrackModel(BaseModel):
         self.fit_init = bool(cfg["init_frame"].get("fit", False))
         self.fit_init_cfg = {"inlier_th": float(cfg["init_frame"].get("inlier_th", INIT_FIT_INLIER_TH)) * float(cfg["data_radius"]),
                              "num_hyps": int(cfg["init_frame"].get("num_hyps", 64)), "seed": int(cfg["init_frame"].get("seed", 0))}
+        # init_frame: {yaxis_only: True} / track_cfg: {guard: {yaxis_only: True}}: the AXIS-ONLY inlier test (include/captra_hip.h,
+        # captra_part_fit_guard_sym) for a symmetric category, whose tracked in-plane angle carries no information.  Absent / False:
+        # today's launches and records; True on a category that is not symmetric is an error.
+        self.fit_init_yaxis = self._yaxis_only(cfg, cfg["init_frame"], "init_frame/yaxis_only")
         self._fit_fallback_logged = False
         # track_cfg: {guard: {...}}: every step checks the pose it produced against the frame's own NOCS map, labels and points
         # (csrc/pose_guard.hip, one launch behind the pose fit, captured with the step) and, with refit, re-fits a part found lost
         # by the first-pose estimator.  Absent: no launch, no tensor, no pickle entry.
         self.guard = self._guard_cfg(cfg)
+        self._warn_full_rotation_test(cfg)
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
         self.radius = cfg["data_radius"]
         self.track_cfg = cfg["track_cfg"]
@@ -185,10 +190,31 @@ class EvalTrackModel(BaseModel):
             raise ValueError("track_cfg/guard needs lost_below (the inlier fraction below which a part counts as lost): it has no default")
         from .pose_utils.pose_fit import lost_ratio
         # lost_below as the two ints the kernel compares with, converted once (raises on a value outside [0, 1])
-        return {"refit": bool(g.get("refit", False)), "lost_below": lost_ratio(g["lost_below"]),
-                "inlier_th": float(g.get("inlier_th", INIT_FIT_INLIER_TH)) * float(cfg["data_radius"]),
-                "min_members": int(g.get("min_members", 4)), "num_hyps": int(g.get("num_hyps", cfg["init_frame"].get("num_hyps", 64))),
-                "seed": int(g.get("seed", cfg["init_frame"].get("seed", 0)))}
+        out = {"refit": bool(g.get("refit", False)), "lost_below": lost_ratio(g["lost_below"]),
+               "inlier_th": float(g.get("inlier_th", INIT_FIT_INLIER_TH)) * float(cfg["data_radius"]),
+               "min_members": int(g.get("min_members", 4)), "num_hyps": int(g.get("num_hyps", cfg["init_frame"].get("num_hyps", 64))),
+               "seed": int(g.get("seed", cfg["init_frame"].get("seed", 0)))}
+        if EvalTrackModel._yaxis_only(cfg, g, "track_cfg/guard/yaxis_only"):
+            out["yaxis_only"] = True            # (carried only when on)
+        return out
+
+    @staticmethod
+    def _yaxis_only(cfg, section, name) -> bool:
+        on = bool(section.get("yaxis_only", False))
+        if on and not cfg["obj_sym"]:
+            raise ValueError(f"{name}: the axis-only inlier test is for symmetric categories (obj_sym), category "
+                             f"{cfg['obj_category']} is not one: its in-plane angle is part of the pose")
+        return on
+
+    def _warn_full_rotation_test(self, cfg):
+        """Once per model object: a symmetric category judged by the full-rotation test."""
+        uses = [name for name, on, yaxis in (("track_cfg/guard", self.guard is not None, self.guard is not None and self.guard.get("yaxis_only", False)),
+                                             ("init_frame/fit", self.fit_init, self.fit_init_yaxis)) if on and not yaxis]
+        if cfg["obj_sym"] and uses:
+            logging.getLogger(__name__).warning(
+                "%s on a symmetric category (%s) with the full-rotation inlier test in use: the tracked in-plane angle carries no "
+                "information there; %s selects the axis-only test", " and ".join(uses), cfg["obj_category"],
+                " / ".join(u.replace("/fit", "") + "/yaxis_only: True" for u in uses))
 
     # ---- host -> device ------------------------------------------------------------------------
     def _gt_part(self, frame):
@@ -261,7 +287,7 @@ class EvalTrackModel(BaseModel):
         mean = first["meta"]["points_mean"].float().to(self.device)
         rot, scale, trans, valid, _ = part_fit_ransac_cn(first["labels"].int().contiguous(), src, first["points"].float().contiguous(),
                                                          num_hyps=self.fit_init_cfg["num_hyps"], inlier_th=self.fit_init_cfg["inlier_th"],
-                                                         seed=self.fit_init_cfg["seed"], target_mean=mean)
+                                                         seed=self.fit_init_cfg["seed"], target_mean=mean, yaxis_only=self.fit_init_yaxis)
         if not self._fit_fallback_logged and not bool(valid.all()):
             self._fit_fallback_logged = True
             logging.getLogger(__name__).warning("init_frame/fit: %d of %d first-pose fits are invalid; those parts start from the "
@@ -404,7 +430,7 @@ class EvalTrackModel(BaseModel):
         pose, info = part_fit_guard_cn(labels, input["pred_nocs"].float().contiguous(), input["points"].float().contiguous(),
                                        input["points_mean"], pose, inlier_th=g["inlier_th"], lost_below=g["lost_below"],
                                        min_members=g["min_members"], refit=g["refit"], num_hyps=g["num_hyps"], seed=g["seed"],
-                                       b0=int(input.get("b0", 0)))
+                                       b0=int(input.get("b0", 0)), yaxis_only=g.get("yaxis_only", False))
         for k in GUARD_KEYS:
             npcs_pred["guard_" + k] = info[k]
         return pose
@@ -767,6 +793,10 @@ class EvalTrackModel(BaseModel):
                      "frame_nums": frame_nums}
         if self.guard is not None:
             save_dict["guard"] = [None if g is None else {k: v.detach().cpu().numpy() for k, v in g.items()} for g in self.pred_dict["guard"]]
+            if self.guard.get("yaxis_only", False):
+                # which test counted the inliers: one boolean, in the slot of frame 0 (which has no record: None otherwise), only
+                # when on -- the frames' records keep their four keys
+                save_dict["guard"][0] = {"yaxis_only": np.ones(len(self.feed_dict[0]["meta"]["path"]), bool)}
         records = []
         for i, path in enumerate(self.feed_dict[0]["meta"]["path"]):
             instance, track_num = path.split(".")[-2].split("/")[-3:-1]

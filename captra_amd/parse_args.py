@@ -26,6 +26,9 @@ _FLAGS = [  # (name, type, default)
     # track health (model.py: EvalTrackModel.guard); lost_below has no default
     ("track_cfg/guard/refit", boolean_string, None), ("track_cfg/guard/lost_below", float, None), ("track_cfg/guard/inlier_th", float, None),
     ("track_cfg/guard/min_members", int, None), ("track_cfg/guard/num_hyps", int, None), ("track_cfg/guard/seed", int, None),
+    # the axis-only inlier test of the symmetric categories, in the guard and in the first-pose fit (init_frame/fit).  Not given = not
+    # in the namespace at all (argparse.SUPPRESS): the key reaches the configuration only when it was written
+    ("track_cfg/guard/yaxis_only", boolean_string, argparse.SUPPRESS), ("init_frame/yaxis_only", boolean_string, argparse.SUPPRESS),
     # optimisation
     ("total_epoch", int, None), ("optimizer", str, None), ("weight_decay", float, None), ("learning_rate", float, None),
     ("lr_policy", str, None), ("lr_gamma", float, None), ("lr_step_size", int, None), ("lr_clip", float, None), ("freq/save", int, None),

@@ -69,12 +69,13 @@ def part_fit_st_no_ransac(labels, source, target, rotation, cfg, given_scale=Non
 
 
 def part_fit_ransac_cn(labels_i32, src_cn, tgt_cn, num_hyps=64, inlier_th=1e-3, sample_rank=None, seed=0, target_mean=None,
-                       tgt_per_part=False, want_samples=False):
+                       tgt_per_part=False, want_samples=False, yaxis_only=False):
     """Channel-major form (no transposes): labels (B,N) int32, src_cn (B,P,3,N), tgt_cn (B,3,N) [or (B,P,3,N) with
     tgt_per_part], target_mean (B,3[,1]) or None (the target is tgt + mean, one fp32 addition in the kernel), sample_rank
     (B,P,H,3) int32 member ranks or None (drawn in the kernel from `seed`, include/captra_hip.h)
     -> rotation (B,P,3,3), scale (B,P), translation (B,P,3,1), valid (B,P) bool, info {'best', 'num_inliers' (B,P) int32
-    [, 'samples' (B,P,H,3) int32 point indices]}.  An invalid fit is identity / 1 / 0."""
+    [, 'samples' (B,P,H,3) int32 point indices]}.  An invalid fit is identity / 1 / 0.
+    yaxis_only: the axis-only inlier test of the symmetric categories (captra_part_fit_ransac_sym)."""
     B, P, _, N = src_cn.shape
     dev = src_cn.device
     if target_mean is not None:
@@ -90,7 +91,7 @@ def part_fit_ransac_cn(labels_i32, src_cn, tgt_cn, num_hyps=64, inlier_th=1e-3, 
     ninl = torch.empty(B, P, dtype=torch.int32, device=dev)
     samples = torch.empty(B, P, num_hyps, 3, dtype=torch.int32, device=dev) if want_samples else None
     with torch.cuda.device(dev):
-        L.call("captra_part_fit_ransac", B, P, N, int(num_hyps), float(inlier_th), L.ptr(labels_i32), L.ptr(src_cn), L.ptr(tgt_cn),
+        L.call("captra_part_fit_ransac_sym" if yaxis_only else "captra_part_fit_ransac", B, P, N, int(num_hyps), float(inlier_th), L.ptr(labels_i32), L.ptr(src_cn), L.ptr(tgt_cn),
                1 if tgt_per_part else 0, L.ptr(target_mean), L.ptr(sample_rank), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(rot), L.ptr(scale),
                L.ptr(trans), L.ptr(valid), L.ptr(best), L.ptr(ninl), L.ptr(samples))
     info = {"best": best, "num_inliers": ninl}
@@ -99,7 +100,8 @@ def part_fit_ransac_cn(labels_i32, src_cn, tgt_cn, num_hyps=64, inlier_th=1e-3, 
     return rot, scale, trans.unsqueeze(-1), valid.bool(), info
 
 
-def part_fit_ransac(labels, source, target, cfg, num_hyps=64, inlier_th=1e-3, sample_rank=None, seed=0, target_mean=None):
+def part_fit_ransac(labels, source, target, cfg, num_hyps=64, inlier_th=1e-3, sample_rank=None, seed=0, target_mean=None,
+                    yaxis_only=False):
     """The reference layouts of part_fit_st_no_ransac: labels (B,N); source (B,P,N,3); target (B,P,N,3) or (B,N,3);
     cfg {'num_parts'} -> ({'rotation' (B,P,3,3), 'scale' (B,P), 'translation' (B,P,3,1)}, valid (B,P) bool,
     info {'best', 'num_inliers'})."""
@@ -108,7 +110,7 @@ def part_fit_ransac(labels, source, target, cfg, num_hyps=64, inlier_th=1e-3, sa
     tgt_cn = target.transpose(-1, -2).float().contiguous()
     rot, scale, trans, valid, info = part_fit_ransac_cn(labels.int().contiguous(), src_cn, tgt_cn, num_hyps=num_hyps, inlier_th=inlier_th,
                                                         sample_rank=sample_rank, seed=seed, target_mean=target_mean,
-                                                        tgt_per_part=target.dim() == 4)
+                                                        tgt_per_part=target.dim() == 4, yaxis_only=yaxis_only)
     return {"rotation": rot, "scale": scale, "translation": trans}, valid, info
 
 
@@ -130,13 +132,14 @@ def lost_ratio(lost_below) -> tuple[int, int]:
 
 
 def part_fit_guard_cn(labels_i32, src_cn, pts_cn, pts_mean, pose, inlier_th, lost_below, min_members=4, refit=False, num_hyps=64,
-                      seed=0, b0=0):
+                      seed=0, b0=0, yaxis_only=False):
     """Track health in one launch (captra_part_fit_guard, include/captra_hip.h): labels (B,N) int32, src_cn (B,P,3,N) predicted
     NOCS, pts_cn (B,3,N), pts_mean (B,3[,1]) or None, pose {'rotation' (B,P,3,3), 'scale' (B,P), 'translation' (B,P,3,1)} = the
     step's pose; lost_below a fraction (see lost_ratio); b0 = the index of the first trajectory within the whole batch.
     -> (pose dict, info {'count', 'inliers' (B,P) int32, 'rms' (B,P) float32, 'verdict' (B,P) int32: GUARD_VERDICTS}).
     refit=False: the pose dict IS `pose` (nothing is written); refit=True: new tensors, the re-fit where verdict == 3 and the input
-    bits everywhere else."""
+    bits everywhere else.  yaxis_only: the axis-only inlier test of the symmetric categories in the check and in the re-fit
+    (captra_part_fit_guard_sym)."""
     B, P, _, N = src_cn.shape
     dev = src_cn.device
     num, den = lost_ratio(lost_below)
@@ -152,7 +155,7 @@ def part_fit_guard_cn(labels_i32, src_cn, pts_cn, pts_mean, pose, inlier_th, los
     verdict = torch.empty(B, P, dtype=torch.int32, device=dev)
     out = (torch.empty_like(rot), torch.empty_like(scale), torch.empty_like(trans)) if refit else (None, None, None)
     with torch.cuda.device(dev):
-        L.call("captra_part_fit_guard", B, P, N, int(b0), L.ptr(labels_i32), L.ptr(src_cn), L.ptr(pts_cn), L.ptr(pts_mean), L.ptr(rot),
+        L.call("captra_part_fit_guard_sym" if yaxis_only else "captra_part_fit_guard", B, P, N, int(b0), L.ptr(labels_i32), L.ptr(src_cn), L.ptr(pts_cn), L.ptr(pts_mean), L.ptr(rot),
                L.ptr(scale), L.ptr(trans), float(inlier_th), num, den, int(min_members), 1 if refit else 0, int(num_hyps),
                int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(count), L.ptr(inliers), L.ptr(rms), L.ptr(verdict), L.ptr(out[0]), L.ptr(out[1]),
                L.ptr(out[2]))

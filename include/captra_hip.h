@@ -673,6 +673,34 @@ int captra_part_fit_guard(int b, int p, int n, int b0, const int *labels, const 
                           int min_members, int refit, int num_hyps, unsigned long long seed, int *count, int *inliers, float *rms,
                           int *verdict, float *rot_out, float *scale_out, float *trans_out, captra_stream_t stream);
 
+/* The AXIS-ONLY inlier test, for the categories whose objects are symmetric about their own y-axis (obj_sym: bottle, bowl, can).
+ * RotationNet predicts their y-axis alone and captra_part_fit_st finds the in-plane angle for itself without returning it, so the
+ * in-plane angle of a tracked rotation carries no information and the full-rotation test above asks it the wrong question.  A
+ * member is an inlier when its camera point lies where its NOCS point's height and radius put it on the surface of revolution; no
+ * angle is estimated.  All fp32, every operation separately rounded:
+ *   a = the second column of rot (rot[0][1], rot[1][1], rot[2][1]), TAKEN AS a unit vector (not normalised); sc, tr = the pose's
+ *   scale and translation; s, t = the member's NOCS point and camera point (t with + mean, as above).
+ *     d_k = t_k - tr_k                      h  = (a0 d0 + a1 d1) + a2 d2
+ *     w_k = d_k - h a_k                     rt = sqrtf((w0 w0 + w1 w1) + w2 w2)
+ *     hs  = sc s_y                          rs = sc sqrtf(s_x s_x + s_z s_z)
+ *     e2  = (h - hs)^2 + (rt - rs)^2        inlier <=> e2 < inlier_th * inlier_th        (a NaN e2 is no inlier)
+ *   (w = d - h a and not |d|^2 - h^2: the latter cancels near the axis.)  The test is invariant under rot -> rot R_y(phi).
+ *
+ * captra_part_fit_guard_sym = captra_part_fit_guard with this test in the check (e2 is also what rms averages) AND in the re-fit,
+ * so both counts of the acceptance rule are counted the same way; captra_part_fit_ransac_sym = captra_part_fit_ransac with this
+ * test in score(h) and in the selection of the winner's inliers, a hypothesis's parameters being a = fp32 of the second column of
+ * its R, sc = fp32(s), tr = fp32(t).  Everything else -- arguments, refused arguments, members, draws, hypotheses, first best,
+ * the refit, validity, the verdict's integer rule, pass-through of the pose -- is as documented above.  The rotation a fit returns
+ * is the full Kabsch rotation of the refit; for a symmetric object its second column is what matters downstream. */
+int captra_part_fit_ransac_sym(int b, int p, int n, int num_hyps, float inlier_th, const int *labels, const float *src, const float *tgt,
+                               int tgt_per_part, const float *tgt_mean, const int *sample_rank, unsigned long long seed, float *rot,
+                               float *scale, float *trans, int *valid, int *best, int *num_inliers, int *samples_out,
+                               captra_stream_t stream);
+int captra_part_fit_guard_sym(int b, int p, int n, int b0, const int *labels, const float *src, const float *pts, const float *pts_mean,
+                              const float *rot, const float *scale, const float *trans, float inlier_th, int lost_num, int lost_den,
+                              int min_members, int refit, int num_hyps, unsigned long long seed, int *count, int *inliers, float *rms,
+                              int *verdict, float *rot_out, float *scale_out, float *trans_out, captra_stream_t stream);
+
 /* CoordinateNet read-out (networks.py:50 F.softmax(dim=1) + model.py:466 torch.max(seg, dim=-2)[1]) in one launch: logits (B,S,N),
  * S <= 8 -> seg (B,S,N) softmax (or NULL), labels (B,N) i32 = FIRST index of the largest logit (or NULL). */
 int captra_seg_softmax_argmax(int b, int s, int n, const float *logits, float *seg, int *labels, captra_stream_t stream);

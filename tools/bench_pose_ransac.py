@@ -5,7 +5,7 @@ on the host.  One JSON line.
 Device figures: `--launches` launches between ONE pair of events per block, median / min / max of `--reps` blocks after a warm-up
 block; microseconds per launch.  Host figure: wall clock of the mirror, median of `--host_reps` calls.
 
-Usage: python tools/bench_pose_ransac.py [--out FILE]
+Usage: python tools/bench_pose_ransac.py [--yaxis-only] [--out FILE]   (--yaxis-only: captra_part_fit_ransac_sym too, same process)
 """
 from __future__ import annotations
 
@@ -65,6 +65,8 @@ def main():
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--host_reps", type=int, default=5)
+    ap.add_argument("--yaxis-only", action="store_true",
+                    help="captra_part_fit_ransac_sym (the axis-only inlier test) too, in the same process: ransac_yaxis_us")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -82,6 +84,11 @@ def main():
             valid, info = ransac()[3:]
             res = {"valid_fits": int(valid.sum()), "inliers_mean": float(info["num_inliers"].float().mean()),
                    "ransac_us": _stats(_timed(ransac, args.launches, args.reps)), "part_fit_st_us": _stats(_timed(st, args.launches, args.reps))}
+            if args.yaxis_only:
+                sym = lambda: part_fit_ransac_cn(d[0], d[1], d[2], num_hyps=args.hyps, inlier_th=float(th), seed=1, yaxis_only=True)   # noqa: E731
+                valid, info = sym()[3:]
+                res.update(valid_fits_yaxis=int(valid.sum()), inliers_mean_yaxis=float(info["num_inliers"].float().mean()),
+                           ransac_yaxis_us=_stats(_timed(sym, args.launches, args.reps)))
             if B == 1:      # the float32 mirror of one part on the host
                 pts = np.nonzero(labels[0] == 0)[0]
                 S, T = src[0, 0][:, pts].T.copy(), tgt[0][:, pts].T.copy()

@@ -7,7 +7,10 @@ Device figures: `--launches` launches (step: `--steps` replays) between ONE pair
 blocks after a warm-up block; microseconds per launch / per step.  The refitting step runs with lost_below = 1, which sends every
 part that has a single outlier into the re-fit: the most the guard can cost.
 
-Usage: python tools/bench_track_guard.py [--out FILE]
+--yaxis-only: every figure a second time, in the same process, with the axis-only inlier test of the symmetric categories
+(captra_part_fit_guard_sym; track_cfg/guard/yaxis_only in the step), under keys that end in `_yaxis`.
+
+Usage: python tools/bench_track_guard.py [--yaxis-only] [--out FILE]
 """
 from __future__ import annotations
 
@@ -61,19 +64,20 @@ def build(B, P, N, seed):
     return labels, src, tgt, np.float32(0.02 * ext), rot, scale, trans
 
 
-def _direct(d, th, hyps, B, P, N, dev):
+def _direct(d, th, hyps, B, P, N, dev, sym=False):
     """The launch alone: the C ABI on pre-allocated outputs, nothing but the ctypes call between the events."""
     from captra_amd import _lib as L
     i32 = [torch.empty(B, P, dtype=torch.int32, device=dev) for _ in range(3)]
     rms = torch.empty(B, P, device=dev)
     po = (torch.empty(B, P, 3, 3, device=dev), torch.empty(B, P, device=dev), torch.empty(B, P, 3, device=dev))
-    fn, stream = L.lib().captra_part_fit_guard, L.stream_ptr()
+    name = "captra_part_fit_guard_sym" if sym else "captra_part_fit_guard"
+    fn, stream = getattr(L.lib(), name), L.stream_ptr()
     fixed = (B, P, N, 0, L.ptr(d[0]), L.ptr(d[1]), L.ptr(d[2]), None)
     outs = (L.ptr(i32[0]), L.ptr(i32[1]), L.ptr(rms), L.ptr(i32[2]), L.ptr(po[0]), L.ptr(po[1]), L.ptr(po[2]), stream)
 
     def run(pose, refit):
         ptrs = (pose["rotation"].data_ptr(), pose["scale"].data_ptr(), pose["translation"].data_ptr())
-        L.check(fn(*fixed, *ptrs, th, 1, 2, 4, 1 if refit else 0, hyps, 1, *outs), "captra_part_fit_guard")
+        L.check(fn(*fixed, *ptrs, th, 1, 2, 4, 1 if refit else 0, hyps, 1, *outs), name)
     run.keep = (i32, rms, po)
     return run
 
@@ -109,10 +113,12 @@ def main():
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--yaxis-only", action="store_true", help="measure the axis-only inlier test too, beside the full-rotation one")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_track_guard needs a GPU")
+    tests = ((False, ""), (True, "_yaxis")) if args.yaxis_only else ((False, ""),)
     dev = torch.device("cuda:0")
     out = {"tool": "bench_track_guard", "device": torch.cuda.get_device_name(0), "N": args.points, "H": args.hyps,
            "timing": f"{args.launches} launches ({args.steps} steps) between one pair of events, us per launch (step), median of blocks"}
@@ -122,17 +128,20 @@ def main():
             d = [torch.from_numpy(a).to(dev) for a in (labels, src, tgt)]
             good = {"rotation": torch.from_numpy(rot).to(dev), "scale": torch.from_numpy(scale).to(dev), "translation": torch.from_numpy(trans).to(dev)}
             bad = dict(good, translation=good["translation"] + 3 * float(th))
-            check = lambda pose, refit: part_fit_guard_cn(d[0], d[1], d[2], None, pose, inlier_th=float(th), lost_below=0.5, refit=refit,   # noqa: E731
-                                                          num_hyps=args.hyps, seed=1)
-            v_ok, v_lost = check(good, False)[1]["verdict"], check(bad, True)[1]["verdict"]
-            run = _direct(d, float(th), args.hyps, B, P, args.points, dev)
-            out[f"B{B}_P{P}"] = {"none_lost_verdicts": np.bincount(v_ok.cpu().numpy().ravel(), minlength=4).tolist(),
-                                 "all_lost_verdicts": np.bincount(v_lost.cpu().numpy().ravel(), minlength=4).tolist(),
-                                 "none_lost_us": _stats(_timed(lambda: run(good, False), args.launches, args.reps)),
-                                 "none_lost_refit_on_us": _stats(_timed(lambda: run(good, True), args.launches, args.reps)),
-                                 "all_lost_refit_us": _stats(_timed(lambda: run(bad, True), args.launches, args.reps))}
-    for name, guard in (("off", None), ("monitoring", {"refit": False, "lost_below": 1.0}), ("refitting", {"refit": True, "lost_below": 1.0})):
-        out[f"step32_{name}"] = step_case(guard, 32, args.steps, args.reps)
+            for sym, sfx in tests:
+                check = lambda pose, refit: part_fit_guard_cn(d[0], d[1], d[2], None, pose, inlier_th=float(th), lost_below=0.5, refit=refit,   # noqa: E731
+                                                              num_hyps=args.hyps, seed=1, yaxis_only=sym)
+                v_ok, v_lost = check(good, False)[1]["verdict"], check(bad, True)[1]["verdict"]
+                run = _direct(d, float(th), args.hyps, B, P, args.points, dev, sym)
+                out[f"B{B}_P{P}{sfx}"] = {"none_lost_verdicts": np.bincount(v_ok.cpu().numpy().ravel(), minlength=4).tolist(),
+                                          "all_lost_verdicts": np.bincount(v_lost.cpu().numpy().ravel(), minlength=4).tolist(),
+                                          "none_lost_us": _stats(_timed(lambda: run(good, False), args.launches, args.reps)),
+                                          "none_lost_refit_on_us": _stats(_timed(lambda: run(good, True), args.launches, args.reps)),
+                                          "all_lost_refit_us": _stats(_timed(lambda: run(bad, True), args.launches, args.reps))}
+    out["step32_off"] = step_case(None, 32, args.steps, args.reps)
+    for sym, sfx in tests:
+        for name, guard in (("monitoring", {"refit": False, "lost_below": 1.0}), ("refitting", {"refit": True, "lost_below": 1.0})):
+            out[f"step32_{name}{sfx}"] = step_case(dict(guard, yaxis_only=True) if sym else guard, 32, args.steps, args.reps)
     line = json.dumps(out)
     print(line)
     if args.out:
