@@ -17,16 +17,27 @@ namespace {
 
 constexpr int CB_T = 1024;
 
+// DET (captra_crop_ball_det): the instance mask of trajectory b is detection sel[b] of det_masks (B,ndet,h,w) -- the mask the detector
+// route selected (crop_box_det_kernel below) -- and mask_all's when sel[b] < 0 (no detection of the category: the reference keeps the
+// pre-fetched mask, nocs_data_process.py:217-218).  The three extra parameters come LAST and the plain instantiation does not touch
+// them: captra_crop_ball's instruction stream is what it was.
+template <bool DET>
 __global__ __launch_bounds__(CB_T) void crop_ball_kernel(int h, int w, int cap, const int *__restrict__ depth_all,
                                                          const unsigned char *__restrict__ mask_all,
                                                          const int *__restrict__ box_all, const double *__restrict__ center_all,
                                                          const double *__restrict__ radius_all, const double *__restrict__ kinv,
                                                          double *__restrict__ pts_all, unsigned char *__restrict__ obj_all,
-                                                         int *__restrict__ pix_all, int *__restrict__ counts) {
+                                                         int *__restrict__ pix_all, int *__restrict__ counts,
+                                                         const unsigned char *__restrict__ det_masks, const int *__restrict__ sel_all,
+                                                         int ndet) {
     __shared__ int wave_tot[2][16];
     const int b = blockIdx.x;
     const int *depth = depth_all + (size_t)b * h * w;
     const unsigned char *mask = mask_all + (size_t)b * h * w;
+    if constexpr (DET) {
+        const int s = sel_all[b];
+        if (s >= 0 && s < ndet) mask = det_masks + ((size_t)b * ndet + s) * h * w;      // (an index outside the stack: the pre-fetched mask)
+    }
     const int r0 = box_all[b * 4 + 0], c0 = box_all[b * 4 + 1], r1 = box_all[b * 4 + 2], c1 = box_all[b * 4 + 3];
     const double cx = center_all[b * 3 + 0], cy = center_all[b * 3 + 1], cz = center_all[b * 3 + 2];
     const double rad = radius_all[b];
@@ -93,14 +104,12 @@ __global__ __launch_bounds__(CB_T) void crop_ball_kernel(int h, int w, int cap, 
 // operation as numpy evaluates captra_amd/nocs_otf.py::proj_corners_batch -- r = max(radius_factor * scale, 0.05); the 8 corners of
 // c +- r times 1000; (-x / z, -y / z, 1); u = (K00 x + K01 y) + K02, v = (K10 x + K11 y) + K12 truncated to int32; rows = h - v, cols = u;
 // min / max over the corners, clamped to the image.  One thread per instance: the box, centre and radius crop_ball_kernel reads.
-__global__ void crop_box_kernel(int b, int h, int w, double radius_factor, const float *__restrict__ trans, const float *__restrict__ scale,
-                                const double *__restrict__ kmat, int *__restrict__ box, double *__restrict__ center,
-                                double *__restrict__ radius) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= b) return;
-    const double c[3] = {(double)trans[i * 3 + 0], (double)trans[i * 3 + 1], (double)trans[i * 3 + 2]};
-    double r = radius_factor * (double)scale[i];
-    r = r > 0.05 ? r : 0.05;                     // numpy.maximum(r, 0.05) (NaN propagates there; a NaN pose has no crop either way)
+__device__ __forceinline__ long long ll_max(long long a, long long b) { return a > b ? a : b; }
+__device__ __forceinline__ long long ll_min(long long a, long long b) { return a < b ? a : b; }
+
+// The projection itself, for the raw radius r_in: -> box[4] = {row_min, col_min, row_max, col_max}; returns the clamped radius.
+__device__ __forceinline__ double crop_box_project(int h, int w, const double c[3], double r_in, const double *__restrict__ kmat, int box[4]) {
+    const double r = r_in > 0.05 ? r_in : 0.05;  // numpy.maximum(r, 0.05) (NaN propagates there; a NaN pose has no crop either way)
     int rmin = 0x7fffffff, rmax = -0x7fffffff - 1, cmin = 0x7fffffff, cmax = -0x7fffffff - 1;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -114,12 +123,93 @@ __global__ void crop_box_kernel(int b, int h, int w, double radius_factor, const
         rmin = row < rmin ? row : rmin; rmax = row > rmax ? row : rmax;
         cmin = col < cmin ? col : cmin; cmax = col > cmax ? col : cmax;
     }
-    box[i * 4 + 0] = rmin > 0 ? rmin : 0;
-    box[i * 4 + 1] = cmin > 0 ? cmin : 0;
-    box[i * 4 + 2] = rmax < h - 1 ? rmax : h - 1;
-    box[i * 4 + 3] = cmax < w - 1 ? cmax : w - 1;
+    box[0] = rmin > 0 ? rmin : 0;
+    box[1] = cmin > 0 ? cmin : 0;
+    box[2] = rmax < h - 1 ? rmax : h - 1;
+    box[3] = cmax < w - 1 ? cmax : w - 1;
+    return r;
+}
+
+__global__ void crop_box_kernel(int b, int h, int w, double radius_factor, const float *__restrict__ trans, const float *__restrict__ scale,
+                                const double *__restrict__ kmat, int *__restrict__ box, double *__restrict__ center,
+                                double *__restrict__ radius) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= b) return;
+    const double c[3] = {(double)trans[i * 3 + 0], (double)trans[i * 3 + 1], (double)trans[i * 3 + 2]};
+    int bx[4];
+    const double r = crop_box_project(h, w, c, radius_factor * (double)scale[i], kmat, bx);
+    box[i * 4 + 0] = bx[0]; box[i * 4 + 1] = bx[1]; box[i * 4 + 2] = bx[2]; box[i * 4 + 3] = bx[3];
     center[i * 3 + 0] = c[0]; center[i * 3 + 1] = c[1]; center[i * 3 + 2] = c[2];
     radius[i] = r;
+}
+
+// The detector route of the re-crop (reference nocs_data_process.py:166-179, 206-229: `--track_cfg/nocs2d_label True`): the instance mask
+// of a frame is the 2D detection of the tracked category whose box overlaps the crop's box best, and the crop's radius grows by 1.2
+// per round while no detection of the category overlaps it by more than 0.05 (until the radius passes 0.5).  Operation by operation as
+// numpy evaluates it: the box of (centre, raw radius) by crop_box_project (the 0.05 clamp inside the projection only); intersection
+// and the three areas as 64-bit integers max(x2 - x1, 0) * max(y2 - y1, 0) (exclusive extents, as the reference has them); the IoU
+// ONE float64 division, times `same`; the selection the FIRST arg max of the last round -- after a give-up with every IoU zero that is
+// detection 0 whatever its class, as in the reference.
+// ONE WAVE per trajectory: lane l takes detections l, l + 64, ... of the det_count[b] real ones (any K: nothing is staged, no cap) and
+// keeps its best (IoU, index) -- `>` keeps the first, its indices ascend --, then six xor-shuffle steps reduce (larger IoU, on a tie
+// the smaller index) so that every lane holds the wave's verdict and the loop's exit test is wave-uniform without LDS or a barrier.
+// The projection is recomputed by every lane (8 corners, ~100 float64 operations per round; the rounds are sequential anyway).
+// Outside the reference's contract: a detection whose union with the box is 0 counts as IoU 0 (numpy: 0/0 = NaN); a growth step that
+// does not enlarge the radius -- NaN, inf, <= 0, or a subnormal that 1.2 x rounds back to itself -- ends the loop at once (the
+// reference would not terminate there).
+__global__ __launch_bounds__(64) void crop_box_det_kernel(int h, int w, int ndet, int category, double radius_factor,
+                                                          const float *__restrict__ trans, const float *__restrict__ scale,
+                                                          const double *__restrict__ kmat, const int *__restrict__ det_boxes,
+                                                          const int *__restrict__ det_class, const int *__restrict__ det_count,
+                                                          int *__restrict__ box, double *__restrict__ center, double *__restrict__ radius,
+                                                          double *__restrict__ radius_raw, int *__restrict__ sel) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const double c[3] = {(double)trans[i * 3 + 0], (double)trans[i * 3 + 1], (double)trans[i * 3 + 2]};
+    double r = radius_factor * (double)scale[i];
+    int cnt = det_count[i];
+    cnt = cnt < 0 ? 0 : (cnt > ndet ? ndet : cnt);
+    const int *db = det_boxes + (size_t)i * ndet * 4;
+    const int *dc = det_class + (size_t)i * ndet;
+    bool any_same = false;
+    for (int k = lane; k < cnt; k += 64) any_same |= dc[k] == category;
+    int bx[4], best_k = -1;
+    double rc;
+    if (__ballot(any_same) == 0ull) {
+        rc = crop_box_project(h, w, c, r, kmat, bx);          // `no same class pred!`: captra_crop_box's outputs, sel = -1
+    } else {
+        for (;;) {
+            rc = crop_box_project(h, w, c, r, kmat, bx);
+            const long long barea = ll_max((long long)bx[3] - bx[1], 0) * ll_max((long long)bx[2] - bx[0], 0);
+            double best = -1.0;
+            best_k = 0x7fffffff;
+            for (int k = lane; k < cnt; k += 64) {
+                const long long y1 = db[k * 4 + 0], x1 = db[k * 4 + 1], y2 = db[k * 4 + 2], x2 = db[k * 4 + 3];
+                const long long iy1 = ll_max(bx[0], y1), iy2 = ll_min(bx[2], y2);
+                const long long ix1 = ll_max(bx[1], x1), ix2 = ll_min(bx[3], x2);
+                const long long inter = ll_max(ix2 - ix1, 0) * ll_max(iy2 - iy1, 0);
+                const long long uni = (barea + ll_max(x2 - x1, 0) * ll_max(y2 - y1, 0)) - inter;
+                const double iou = (dc[k] == category && uni != 0) ? (double)inter / (double)uni : 0.0;
+                if (iou > best) { best = iou; best_k = k; }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const double ob = __shfl_xor(best, off, 64);
+                const int ok = __shfl_xor(best_k, off, 64);
+                if (ob > best || (ob == best && ok < best_k)) { best = ob; best_k = ok; }
+            }
+            if (best > 0.05 || r > 0.5) break;
+            const double grown = r * 1.2;
+            if (!(grown > r)) break;
+            r = grown;
+        }
+    }
+    if (lane == 0) {
+        box[i * 4 + 0] = bx[0]; box[i * 4 + 1] = bx[1]; box[i * 4 + 2] = bx[2]; box[i * 4 + 3] = bx[3];
+        center[i * 3 + 0] = c[0]; center[i * 3 + 1] = c[1]; center[i * 3 + 2] = c[2];
+        radius[i] = rc;
+        radius_raw[i] = r;
+        sel[i] = best_k;
+    }
 }
 
 // ---- the re-crop's candidate lists and its read-out without the host --------------------------------------
@@ -201,8 +291,32 @@ extern "C" int captra_crop_ball(int b, int h, int w, int cap, const int *depth, 
                                 unsigned char *obj, int *pix, int *counts, captra_stream_t stream) {
     if (b < 0 || h < 1 || w < 1 || cap < 1) return -1;
     if (b == 0) return 0;
-    CAPTRA_LAUNCH("crop_ball", crop_ball_kernel, dim3(b), dim3(CB_T), 0, (hipStream_t)stream, h, w, cap, depth, mask, box,
-                  center, radius, kinv, pts, obj, pix, counts);
+    CAPTRA_LAUNCH("crop_ball", crop_ball_kernel<false>, dim3(b), dim3(CB_T), 0, (hipStream_t)stream, h, w, cap, depth, mask, box,
+                  center, radius, kinv, pts, obj, pix, counts, (const unsigned char *)nullptr, (const int *)nullptr, 0);
+    return captra_last_error();
+}
+
+// The detector route (see crop_box_det_kernel): captra_crop_box's outputs after the reference's radius growth, the radius as the
+// reference hands it on (radius_raw: unclamped) and the selected detection per trajectory (sel, -1 = none of the category).
+extern "C" int captra_crop_box_det(int b, int h, int w, int ndet, int category, double radius_factor, const float *trans, const float *scale,
+                                   const double *kmat, const int *det_boxes, const int *det_class, const int *det_count, int *box,
+                                   double *center, double *radius, double *radius_raw, int *sel, captra_stream_t stream) {
+    if (b < 0 || h < 1 || w < 1 || ndet < 0) return -1;
+    if (b == 0) return 0;
+    CAPTRA_LAUNCH("crop_ball", crop_box_det_kernel, dim3(b), dim3(64), 0, (hipStream_t)stream, h, w, ndet, category, radius_factor, trans,
+                  scale, kmat, det_boxes, det_class, det_count, box, center, radius, radius_raw, sel);
+    return captra_last_error();
+}
+
+// captra_crop_ball with the instance mask of trajectory i taken from det_masks (B,ndet,h,w) at detection sel[i], and from mask where sel[i] < 0.
+extern "C" int captra_crop_ball_det(int b, int h, int w, int cap, int ndet, const int *depth, const unsigned char *mask,
+                                    const unsigned char *det_masks, const int *sel, const int *box, const double *center,
+                                    const double *radius, const double *kinv, double *pts, unsigned char *obj, int *pix, int *counts,
+                                    captra_stream_t stream) {
+    if (b < 0 || h < 1 || w < 1 || cap < 1 || ndet < 0) return -1;
+    if (b == 0) return 0;
+    CAPTRA_LAUNCH("crop_ball", crop_ball_kernel<true>, dim3(b), dim3(CB_T), 0, (hipStream_t)stream, h, w, cap, depth, mask, box,
+                  center, radius, kinv, pts, obj, pix, counts, det_masks, sel, ndet);
     return captra_last_error();
 }
 

@@ -31,6 +31,7 @@ import torch.nn as nn
 from . import fused
 from . import graph as G
 from .networks import CoordNet, PartCanonNet, _canonicalize
+from .nocs_otf import DET_KEYS
 from .pose_utils.part_dof_utils import add_noise_to_part_dof, consume_noise_draws, eval_part_full, part_model_batch_to_part
 from .utils import Timer, add_dict, cvt_torch, divide_dict, ensure_dirs, get_ith_from_batch
 
@@ -140,6 +141,8 @@ class EvalTrackModel(BaseModel):
         self._warn_full_rotation_test(cfg)
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
         self.radius = cfg["data_radius"]
+        self.det_category = cfg["obj_category"]          # nocs2d_label: the class id the frame's detections are matched against
+        self._det_missing_logged = False
         self.track_cfg = cfg["track_cfg"]
         self.npcs_feed_dict = []
         self.timer = Timer(True)
@@ -237,6 +240,10 @@ class EvalTrackModel(BaseModel):
         if pre is not None:      # nocs_otf: the frame's depth image and instance mask live on the device
             out["pre_fetched"] = {"depth": torch.as_tensor(pre["depth"]).to(self.device).int(),
                                   "mask": torch.as_tensor(pre["mask"]).to(self.device).bool()}
+            if self.track_cfg["nocs2d_label"] and all(k in pre for k in DET_KEYS):
+                # the frame's 2D detections (boxes, classes, count, masks): the re-crop selects among them on the device
+                out["pre_fetched"].update({k: torch.as_tensor(pre[k]).to(self.device).to(torch.uint8 if k == "det_masks" else torch.int32).contiguous()
+                                           for k in DET_KEYS})
             # the re-crop derives ground-truth NOCS from the root part's ground-truth pose: keep it on the host (float64,
             # the values of the float32 device copy), so that the loop does not fetch it back from the device every frame
             root = frame["meta"]["nocs2camera"][self.root]
@@ -522,24 +529,48 @@ class EvalTrackModel(BaseModel):
             gt = {k: to_host(v[:, self.root].double().contiguous()) for k, v in input["gt_part"].items()}
         gt = {k: v[sl] for k, v in gt.items()}
         depth, mask = pre["depth"][sl], pre["mask"][sl]
+        det = self._detections(pre, sl)
         gt64 = {"rotation": np.asarray(gt["rotation"], np.float64).reshape(b, 3, 3),
                 "translation": np.asarray(gt["translation"], np.float64).reshape(b, 3),
                 "scale": np.asarray(gt["scale"], np.float64).reshape(b)}
         gtd = input.get("gt_root_dev")
         gtd = None if gtd is None else {k: v[sl] for k, v in gtd.items()}
         trans_d, scale_d = last_pose["translation"][:, self.root].reshape(b, 3), last_pose["scale"][:, self.root].reshape(b)
-        if OTF_POSE_ON_DEVICE and depth.is_cuda and trans_d.dtype == torch.float32 and scale_d.dtype == torch.float32:
+        if (OTF_POSE_ON_DEVICE or det is not None) and depth.is_cuda and trans_d.dtype == torch.float32 and scale_d.dtype == torch.float32:
             # the crop's box / centre / radius derived on the device from the pose (captra_crop_box): no round trip for the pose
+            # (the detector route exists in this form only: its selection is captra_crop_box_det)
             full = full_data_batch_arrays(depth, mask, None, None, gt64, N, stacked=True, pose_dev=(trans_d, scale_d, float(self.radius)), gt_dev=gtd,
-                                          defer=defer, mean=npcs["points_mean"][sl])
+                                          defer=defer, mean=npcs["points_mean"][sl], det=det)
             if defer is not None:
                 return full["points_cn"], full["labels"], full["nocs_cn"], full["_info"]
+        elif det is not None:
+            raise ValueError("track_cfg/nocs2d_label with detections in the frame: the selection runs on the device from an fp32 pose")
         else:
             defer = None
             cs = to_host(torch.cat([trans_d, scale_d.reshape(b, 1)], dim=1).double())
             full = full_data_batch_arrays(depth, mask, cs[:, :3], self.radius * cs[:, 3], gt64, N, stacked=True)
         points = (full["points"].float() - npcs["points_mean"][sl].reshape(b, 1, 3)).transpose(1, 2).contiguous()
         return points, full["labels"].contiguous(), full["nocs"].float().transpose(1, 2).contiguous()
+
+    def _detections(self, pre, sl):
+        """The detector route's inputs for the trajectories `sl` (reference model.py:437-439 -> nocs_data_process.py:206-229), or None:
+        taken when track_cfg/nocs2d_label is set AND the frame carries its detections (meta['pre_fetched'] det_*).  With the flag set
+        and no detections the pre-fetched mask is used, as before -- said once per model object."""
+        if not self.track_cfg["nocs2d_label"]:
+            return None
+        if not all(k in pre for k in DET_KEYS):
+            if not self._det_missing_logged:
+                self._det_missing_logged = True
+                logging.getLogger(__name__).warning("track_cfg/nocs2d_label is set but the frames carry no detections (meta['pre_fetched'] %s): "
+                                                    "the re-crop uses the pre-fetched instance mask", " / ".join(DET_KEYS))
+            return None
+        try:
+            category = int(self.det_category)
+        except (TypeError, ValueError):
+            raise ValueError(f"track_cfg/nocs2d_label: the detections' class ids are integers, category {self.det_category!r} is not one") from None
+        det = {k: pre[k][sl] for k in DET_KEYS}
+        det["category"] = category
+        return det
 
     def _recrop(self, i, input, last_pose, defer=None):
         """The whole batch of frame i re-cropped in place (input / npcs feed dicts); -> the deferred check's device word or None."""

@@ -250,8 +250,11 @@ def _arange(n: int, dev) -> torch.Tensor:
     return _ARANGE[key]
 
 
+DET_KEYS = ("det_boxes", "det_class", "det_count", "det_masks")
+
+
 def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, intrinsics=NOCS_REAL_INTRINSICS, stacked: bool = True,
-                           pose_dev=None, gt_dev=None, defer=None, mean=None):
+                           pose_dev=None, gt_dev=None, defer=None, mean=None, det=None):
     """full_data_batch on already-stacked inputs (the track loop's form: no per-trajectory Python on the frame's critical
     path): depth (B,H,W), mask (B,H,W) device tensors; centers (B,3), radii_in (B,) float64 host arrays (radius as handed to
     full_data_from_depth: clamped to 0.05 inside); gt = {'rotation' (B,3,3), 'translation' (B,3), 'scale' (B,)} float64 host arrays.
@@ -262,13 +265,29 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
     `defer` (with pose_dev; an int = upper bound of the candidate lists' length): NO round trip at all -- see the branch below; the
     result is then {'points_cn' (B,3,N) fp32 = points - `mean` (B,3), 'labels' (B,N), 'nocs_cn' (B,3,N) fp32, '_info'}: the
     frame's tensors in the networks' layouts (captra_otf_finish) and the device int32 word [a rare-path instance was met, longest
-    list, ..] for the caller to read a frame late."""
+    list, ..] for the caller to read a frame late.
+    `det` (with pose_dev) = the detector route (reference nocs_data_process.py:206-229, `nocs2d_label`): {'det_boxes' (B,K,4) int32
+    [y1,x1,y2,x2], 'det_class' (B,K) int32, 'det_count' (B,) int32, 'det_masks' (B,K,H,W) uint8, 'category' int} device tensors -- every
+    trajectory crops with the mask of the detection of its category that overlaps its (grown) box best (captra_crop_box_det selects,
+    captra_crop_ball_det reads that mask: two launches in place of two, nothing visits the host), `mask` where there is none."""
     from . import _lib as L, fused
     dev = depth.device
     B = depth.shape[0]
     depth = depth.to(torch.int32).contiguous()
     mask = mask.to(torch.uint8).contiguous()
     _, H, W = depth.shape
+    if det is not None:
+        if pose_dev is None or dev.type != "cuda":
+            raise ValueError("the detector route of the re-crop selects its masks on the device: it takes the pose as `pose_dev`")
+        det_boxes = det["det_boxes"].to(torch.int32).contiguous()
+        K = det_boxes.shape[1]
+        det_class = det["det_class"].to(torch.int32).contiguous()
+        det_count = det["det_count"].to(torch.int32).contiguous()
+        det_masks = det["det_masks"].to(torch.uint8).contiguous()
+        if (tuple(det_boxes.shape) != (B, K, 4) or tuple(det_class.shape) != (B, K) or tuple(det_count.shape) != (B,)
+                or tuple(det_masks.shape) != (B, K, H, W)):
+            raise ValueError(f"detections of a frame: det_boxes (B,K,4), det_class (B,K), det_count (B,), det_masks (B,K,H,W) with B = {B}, "
+                             f"H x W = {H} x {W}; got {tuple(det_boxes.shape)}, {tuple(det_class.shape)}, {tuple(det_count.shape)}, {tuple(det_masks.shape)}")
     pts = torch.empty(B, CROP_CAP, 3, dtype=torch.float64, device=dev)
     obj = torch.empty(B, CROP_CAP, dtype=torch.uint8, device=dev)
     pix = torch.empty(B, CROP_CAP, dtype=torch.int32, device=dev)
@@ -282,9 +301,17 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
         ctr_d = torch.empty(B, 3, dtype=torch.float64, device=dev)
         rad_d = torch.empty(B, dtype=torch.float64, device=dev)
         with torch.cuda.device(dev):
-            L.call("captra_crop_box", B, H, W, float(factor), L.ptr(trans_d), L.ptr(scale_d), kk.data_ptr(), L.ptr(box_d), L.ptr(ctr_d), L.ptr(rad_d))
-            L.call("captra_crop_ball", B, H, W, CROP_CAP, L.ptr(depth), L.ptr(mask), L.ptr(box_d), L.ptr(ctr_d), L.ptr(rad_d),
-                   kk.data_ptr() + 72, L.ptr(pts), L.ptr(obj), L.ptr(pix), L.ptr(counts))
+            if det is not None:
+                raw_d = torch.empty(B, dtype=torch.float64, device=dev)
+                sel_d = torch.empty(B, dtype=torch.int32, device=dev)
+                L.call("captra_crop_box_det", B, H, W, K, int(det["category"]), float(factor), L.ptr(trans_d), L.ptr(scale_d), kk.data_ptr(),
+                       L.ptr(det_boxes), L.ptr(det_class), L.ptr(det_count), L.ptr(box_d), L.ptr(ctr_d), L.ptr(rad_d), L.ptr(raw_d), L.ptr(sel_d))
+                L.call("captra_crop_ball_det", B, H, W, CROP_CAP, K, L.ptr(depth), L.ptr(mask), L.ptr(det_masks), L.ptr(sel_d), L.ptr(box_d),
+                       L.ptr(ctr_d), L.ptr(rad_d), kk.data_ptr() + 72, L.ptr(pts), L.ptr(obj), L.ptr(pix), L.ptr(counts))
+            else:
+                L.call("captra_crop_box", B, H, W, float(factor), L.ptr(trans_d), L.ptr(scale_d), kk.data_ptr(), L.ptr(box_d), L.ptr(ctr_d), L.ptr(rad_d))
+                L.call("captra_crop_ball", B, H, W, CROP_CAP, L.ptr(depth), L.ptr(mask), L.ptr(box_d), L.ptr(ctr_d), L.ptr(rad_d),
+                       kk.data_ptr() + 72, L.ptr(pts), L.ptr(obj), L.ptr(pix), L.ptr(counts))
     else:
         centers = np.ascontiguousarray(np.asarray(centers, np.float64).reshape(B, 3))
         radii_in = np.asarray(radii_in, np.float64).reshape(B)
@@ -333,9 +360,15 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
                    L.ptr(rot), L.ptr(trans), L.ptr(scale), L.ptr(points_cn), L.ptr(labels), L.ptr(nocs_cn))
         return {"points_cn": points_cn, "labels": labels, "nocs_cn": nocs_cn, "_info": info}
     n_members = to_host(counts[:, 0].contiguous())                                               # the one sync of the stage
+    sel_h = None
     if pose_dev is not None and any(int(c) < 10 or int(c) > CROP_CAP for c in n_members):
         # a rare-path instance (radius growth / more members than the table holds) takes the torch path, which wants the centre on the host
-        cs = to_host(torch.cat([ctr_d, (float(factor) * scale_d.double()).reshape(B, 1)], dim=1))
+        # (the detector route: and the radius as the selection grew it, and the selection -- exact in a float64 -- in the same round trip)
+        if det is not None:
+            cs = to_host(torch.cat([ctr_d, raw_d.reshape(B, 1), sel_d.double().reshape(B, 1)], dim=1))
+            sel_h = cs[:, 4].astype(np.int64)
+        else:
+            cs = to_host(torch.cat([ctr_d, (float(factor) * scale_d.double()).reshape(B, 1)], dim=1))
         centers, radii_in = np.ascontiguousarray(cs[:, :3]), np.ascontiguousarray(cs[:, 3])
 
     def gt_of(b):
@@ -347,7 +380,8 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
     for b in range(B):
         c = int(n_members[b])
         if c < 10 or c > CROP_CAP:
-            slow[b] = crop_candidates(depth[b], mask[b].bool(), centers[b], float(radii_in[b]), num_points, intrinsics)
+            mask_b = det_masks[b, int(sel_h[b])] if sel_h is not None and sel_h[b] >= 0 else mask[b]
+            slow[b] = crop_candidates(depth[b], mask_b.bool(), centers[b], float(radii_in[b]), num_points, intrinsics)
             continue
         length = c
         while length < num_points:

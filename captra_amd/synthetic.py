@@ -352,5 +352,56 @@ def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float =
     return data
 
 
+def _shift2d(a: np.ndarray, dr: int, dc: int) -> np.ndarray:
+    """`a` moved by (dr, dc) pixels, zeros moving in."""
+    out = np.zeros_like(a)
+    H, W = a.shape
+    out[max(dr, 0):H + min(dr, 0), max(dc, 0):W + min(dc, 0)] = a[max(-dr, 0):H + min(-dr, 0), max(-dc, 0):W + min(-dc, 0)]
+    return out
+
+
+def make_otf_detections(batch: int, frames: int, seed: int = 0, step_px: float = 6.0, num_det: int = 4, category: int = 1, data=None):
+    """make_otf_trajectory's frames carrying seeded 2D detections per frame (meta['pre_fetched'] det_boxes (B,K,4) int32 [y1,x1,y2,x2],
+    det_class (B,K) int32, det_count (B,) int32, det_masks (B,K,H,W) uint8; K = num_det) -- the detector route of the re-crop
+    (`--track_cfg/nocs2d_label True`, reference nocs_data_process.py:206-229).  One detection per frame FOLLOWS the blob: class
+    `category`, mask = the ground-truth mask moved by (2, 3) pixels (so that cropping with it differs from cropping with the ground
+    truth), box = that mask's bounding box, in a seeded slot.  The others are distractors of other classes: one over the blob's own
+    box grown by 20 pixels (the larger overlap with the crop's box must not win), the rest rectangles anywhere in the image.
+    `data`: frames of make_otf_trajectory(batch, frames, seed, step_px) to extend (generated when None)."""
+    if num_det < 1:
+        raise ValueError("num_det >= 1")
+    if data is None:
+        data = make_otf_trajectory(batch, frames, seed=seed, step_px=step_px)
+    for t, f in enumerate(data):
+        masks = np.asarray(f["meta"]["pre_fetched"]["mask"]).astype(bool)
+        H, W = masks.shape[1:]
+        boxes = np.zeros((batch, num_det, 4), np.int32)
+        cls = np.zeros((batch, num_det), np.int32)
+        dmask = np.zeros((batch, num_det, H, W), np.uint8)
+        for b in range(batch):
+            rng = np.random.default_rng([seed + b, t, 2206])
+            follow = int(rng.integers(num_det))
+            m = _shift2d(masks[b], 2, 3)
+            rows, cols = np.where(m.any(1))[0], np.where(m.any(0))[0]
+            fbox = np.array([rows[0], cols[0], rows[-1], cols[-1]], np.int32)
+            first = True
+            for k in range(num_det):
+                if k == follow:
+                    boxes[b, k], cls[b, k], dmask[b, k] = fbox, category, m
+                    continue
+                if first:          # a wrong-class detection around the blob
+                    y1, x1, y2, x2 = max(fbox[0] - 20, 0), max(fbox[1] - 20, 0), min(fbox[2] + 20, H - 1), min(fbox[3] + 20, W - 1)
+                    first = False
+                else:
+                    y1, x1 = int(rng.integers(0, H - 40)), int(rng.integers(0, W - 40))
+                    y2, x2 = min(y1 + int(rng.integers(20, 160)), H - 1), min(x1 + int(rng.integers(20, 160)), W - 1)
+                boxes[b, k] = (y1, x1, y2, x2)
+                cls[b, k] = category + 1 + int(rng.integers(5))
+                dmask[b, k, y1:y2 + 1, x1:x2 + 1] = 1
+        f["meta"]["pre_fetched"].update({"det_boxes": torch.from_numpy(boxes), "det_class": torch.from_numpy(cls),
+                                         "det_count": torch.full((batch,), num_det, dtype=torch.int32), "det_masks": torch.from_numpy(dmask)})
+    return data
+
+
 # G15 fixture (tests/golden/make_golden_otf_loop.py): tag -> (frames, trajectory seed, weight seed, torch / numpy seed)
 OTF_LOOP_SETUPS = {"a": (5, 1, 31, 5001), "b": (4, 2, 32, 5002)}

@@ -170,17 +170,28 @@ def _trajectory_sources(args, cfg):
     return files
 
 
-def _load_source(src, args):
+def _load_source(src, args, cfg=None):
     """One trajectory as a list over frames of batch-1 frame dicts.  A synthetic trajectory is generated from its own seed
-    (batch 1), so its content does not depend on the rank or the batch it is tracked in."""
+    (batch 1), so its content does not depend on the rank or the batch it is tracked in.  With nocs_otf the synthetic frames carry
+    their depth images and masks (make_otf_trajectory) and, with track_cfg/nocs2d_label, seeded 2D detections (make_otf_detections);
+    trajectory files without detections take them from the detector result files under track_cfg/nocs2d_path."""
+    otf = bool(cfg and cfg.get("nocs_otf"))
+    det = otf and bool(cfg["track_cfg"].get("nocs2d_label"))
     if isinstance(src, tuple):
         try:
             from captra_amd import synthetic as clouds
         except ImportError as e:  # pragma: no cover
             raise SystemExit("--data synthetic needs the repository's tests/ package on sys.path") from e
         _, kind, seed = src
+        if otf and kind == "nocs":
+            make = clouds.make_otf_detections if det else clouds.make_otf_trajectory
+            return make(1, args.num_frames, seed=seed)
         return clouds.make_trajectory(kind, 1, args.num_frames, seed=seed)
-    return stack_trajectories([load_trajectory_npz(src)])
+    frames = stack_trajectories([load_trajectory_npz(src)])
+    if det and cfg["track_cfg"].get("nocs2d_path") and "pre_fetched" in frames[0]["meta"] and "det_boxes" not in frames[0]["meta"]["pre_fetched"]:
+        from .trajectory_io import attach_nocs2d_detections
+        attach_nocs2d_detections(frames, cfg["track_cfg"]["nocs2d_path"])
+    return frames
 
 
 def iter_batches(args, cfg, ranks: Ranks | None = None):
@@ -192,7 +203,7 @@ def iter_batches(args, cfg, ranks: Ranks | None = None):
     sources = _trajectory_sources(args, cfg)
     if ranks is not None and ranks.world > 1:
         sources = [sources[g] for g in shard_range(len(sources), ranks.world, ranks.rank)]
-    trajs = [_load_source(s, args) for s in sources]
+    trajs = [_load_source(s, args, cfg) for s in sources]
     if not args.data.startswith("synthetic"):
         trajs.sort(key=lambda t: len(t))                     # equal-length trajectories batch together
     i = 0

@@ -14,6 +14,9 @@ per trajectory -- the arrays a dataset item holds after cropping to N points:
     paths        (T,) str      "…/<instance>/<track>/<frame>.<ext>" (drives the result file names, model.py:497-509)
     depth, mask  (T,H,W) uint16 mm / bool, optional: the frames' depth images and instance masks for `--nocs_otf True`
                                (the reference's meta['pre_fetched'], dataset.py:157-194)
+    det_boxes (T,K,4) i32 [y1,x1,y2,x2], det_class (T,K) i32, det_count (T,) i32, det_masks (T,K,H,W) u8, optional (with depth / mask):
+                               the frames' 2D detections for `--track_cfg/nocs2d_label True`, K slots of which the first det_count hold one
+    ori_paths    (T,) str      optional: "…/<scene>/<frame>_depth.png" (meta['ori_path']): names the detector result file of a frame
 
 `stack_trajectories` batches B trajectories of equal length into the (B, …) frame dicts `set_data` takes.
 """
@@ -23,6 +26,8 @@ import numpy as np
 import torch
 
 _KEYS = ("points", "points_mean", "labels", "nocs", "rotation", "translation", "scale", "nocs_corners", "paths")
+DET_KEYS = ("det_boxes", "det_class", "det_count", "det_masks")
+_DET_DTYPES = {"det_boxes": np.int32, "det_class": np.int32, "det_count": np.int32, "det_masks": np.uint8}
 
 
 def save_trajectory_npz(path: str, frames: list, b: int = 0) -> None:
@@ -42,6 +47,11 @@ def save_trajectory_npz(path: str, frames: list, b: int = 0) -> None:
     if all("pre_fetched" in f["meta"] for f in frames):
         out["depth"] = np.stack([np.asarray(f["meta"]["pre_fetched"]["depth"][b]) for f in frames]).astype(np.uint16)
         out["mask"] = np.stack([np.asarray(f["meta"]["pre_fetched"]["mask"][b]) for f in frames]).astype(bool)
+        if all(k in f["meta"]["pre_fetched"] for f in frames for k in DET_KEYS):
+            for k in DET_KEYS:
+                out[k] = np.stack([np.asarray(f["meta"]["pre_fetched"][k][b]) for f in frames]).astype(_DET_DTYPES[k])
+    if all("ori_path" in f["meta"] for f in frames):
+        out["ori_paths"] = np.array([f["meta"]["ori_path"][b] for f in frames])
     np.savez(path, **out)
 
 
@@ -51,7 +61,7 @@ def load_trajectory_npz(path: str) -> dict:
         if missing:
             raise ValueError(f"{path}: not a trajectory file, missing {missing}")
         traj = {k: z[k] for k in _KEYS}
-        for k in ("depth", "mask"):
+        for k in ("depth", "mask", "ori_paths") + DET_KEYS:
             if k in z.files:
                 traj[k] = z[k]
     T = traj["points"].shape[0]
@@ -77,6 +87,10 @@ def stack_trajectories(trajs: list) -> list:
         if all("depth" in t and "mask" in t for t in trajs):
             meta["pre_fetched"] = {"depth": torch.from_numpy(np.stack([t["depth"][i].astype(np.int32) for t in trajs])),
                                    "mask": torch.from_numpy(np.stack([t["mask"][i] for t in trajs]))}
+            if all(k in t for t in trajs for k in DET_KEYS):
+                meta["pre_fetched"].update(pad_detections([{k: t[k][i] for k in DET_KEYS} for t in trajs]))
+        if all("ori_paths" in t for t in trajs):
+            meta["ori_path"] = [str(t["ori_paths"][i]) for t in trajs]
         frames.append({"points": cat("points"), "labels": cat("labels", torch.int64), "nocs": cat("nocs"), "meta": meta})
     return frames
 
@@ -102,6 +116,70 @@ def concat_frame_batches(batches: list) -> list:
                 "nocs_corners": torch.cat([f["meta"]["nocs_corners"] for f in frames])}
         if all("pre_fetched" in f["meta"] for f in frames):
             meta["pre_fetched"] = {k: torch.cat([torch.as_tensor(f["meta"]["pre_fetched"][k]) for f in frames]) for k in ("depth", "mask")}
+            if all(k in f["meta"]["pre_fetched"] for f in frames for k in DET_KEYS):
+                meta["pre_fetched"].update(pad_detections([{k: f["meta"]["pre_fetched"][k] for k in DET_KEYS} for f in frames], batched=True))
+        if all("ori_path" in f["meta"] for f in frames):
+            meta["ori_path"] = [p for f in frames for p in f["meta"]["ori_path"]]
         out.append({"points": torch.cat([f["points"] for f in frames]), "labels": torch.cat([f["labels"] for f in frames]),
                     "nocs": torch.cat([f["nocs"] for f in frames]), "meta": meta})
     return out
+
+
+def pad_detections(items: list, batched: bool = False, slots: int | None = None) -> dict:
+    """Detections of one frame from several sources -> one batch: the K axis padded to the largest K (or `slots`) with empty slots
+    (box 0, class -1, mask 0; det_count says how many are real).  items: dicts of det_boxes (K,4), det_class (K,), det_count (),
+    det_masks (K,H,W) -- or, `batched`, of (b,K,4), (b,K), (b,), (b,K,H,W) -- arrays or tensors -> dict of CPU tensors (B, ...)."""
+    arrs = [{k: np.asarray(it[k]) if not torch.is_tensor(it[k]) else it[k].cpu().numpy() for k in DET_KEYS} for it in items]
+    if not batched:
+        arrs = [{k: a[k][None] for k in DET_KEYS} for a in arrs]
+    K = max([a["det_boxes"].shape[1] for a in arrs] + [int(slots or 0)])
+    H, W = arrs[0]["det_masks"].shape[-2:]
+    out = {"det_boxes": [], "det_class": [], "det_count": [], "det_masks": []}
+    for a in arrs:
+        b, k = a["det_boxes"].shape[:2]
+        boxes = np.zeros((b, K, 4), np.int32)
+        cls = np.full((b, K), -1, np.int32)
+        masks = np.zeros((b, K, H, W), np.uint8)
+        boxes[:, :k], cls[:, :k], masks[:, :k] = a["det_boxes"], a["det_class"], a["det_masks"]
+        out["det_boxes"].append(boxes)
+        out["det_class"].append(cls)
+        out["det_masks"].append(masks)
+        out["det_count"].append(np.asarray(a["det_count"], np.int32).reshape(b))
+    return {k: torch.from_numpy(np.concatenate(v)) for k, v in out.items()}
+
+
+def load_nocs2d_result(nocs2d_path: str, scene: str, frame: str, slots: int | None = None) -> dict:
+    """One frame's detections from the reference's detector result file `results_test_{scene}_{frame}.pkl` under `nocs2d_path`
+    (nocs_data_process.py:206-214; keys pred_class_ids (n,), pred_bboxes (n,4) [y1,x1,y2,x2], pred_masks (H,W,n)) -> det_boxes (K,4) int32,
+    det_class (K,) int32, det_count () int32 = n, det_masks (K,H,W) uint8 with K = max(n, slots, 1): the slots past n are empty."""
+    import pickle
+    from os.path import join as pjoin
+    with open(pjoin(nocs2d_path, f"results_test_{scene}_{frame}.pkl"), "rb") as f:
+        res = pickle.load(f)
+    cls = np.asarray(res["pred_class_ids"]).reshape(-1)
+    n = cls.shape[0]
+    masks = np.asarray(res["pred_masks"])
+    if masks.ndim != 3 or masks.shape[2] != n or np.asarray(res["pred_bboxes"]).reshape(-1, 4).shape[0] != n:
+        raise ValueError(f"{nocs2d_path}: results_test_{scene}_{frame}.pkl: {n} class ids, boxes {np.asarray(res['pred_bboxes']).shape}, masks {masks.shape}")
+    K = max(n, int(slots or 0), 1)
+    out = {"det_boxes": np.zeros((K, 4), np.int32), "det_class": np.full((K,), -1, np.int32), "det_count": np.int32(n),
+           "det_masks": np.zeros((K,) + masks.shape[:2], np.uint8)}
+    out["det_boxes"][:n] = np.asarray(res["pred_bboxes"]).reshape(n, 4)
+    out["det_class"][:n] = cls
+    out["det_masks"][:n] = np.moveaxis(masks != 0, 2, 0)
+    return out
+
+
+def attach_nocs2d_detections(frames: list, nocs2d_path: str, slots: int | None = None) -> list:
+    """Batched frame dicts with meta['ori_path'] (".../<scene>/<frame>_depth.png", the reference's depth path: scene = its directory,
+    frame = the first four characters of its name) and meta['pre_fetched'] -> the same frames carrying their detections from
+    `nocs2d_path` (load_nocs2d_result per trajectory and frame, padded to one K per frame)."""
+    for f in frames:
+        if "ori_path" not in f["meta"] or "pre_fetched" not in f["meta"]:
+            raise ValueError("detections are attached by the frames' depth paths (meta['ori_path']) to their depth / mask (meta['pre_fetched'])")
+        items = []
+        for path in f["meta"]["ori_path"]:
+            scene, name = str(path).split("/")[-2:]
+            items.append(load_nocs2d_result(nocs2d_path, scene, name[:4], slots))
+        f["meta"]["pre_fetched"].update(pad_detections(items, slots=slots))
+    return frames

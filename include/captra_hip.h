@@ -429,6 +429,30 @@ int captra_crop_ball(int b, int h, int w, int cap, const int *depth, const unsig
  * with numpy's operation order and int32 truncation.  What captra_crop_ball reads: no host round trip between the pose and the crop. */
 int captra_crop_box(int b, int h, int w, double radius_factor, const float *trans, const float *scale, const double *kmat, int *box,
                     double *center, double *radius, captra_stream_t stream);
+/* The detector route of the re-crop (reference nocs_data_process.py:166-179, 206-229, `--track_cfg/nocs2d_label True`): the frame's
+ * instance mask is the 2D detection of the tracked category whose box overlaps the crop's box best.  Per trajectory i, with
+ * det_boxes (B,ndet,4) int32 {y1, x1, y2, x2}, det_class (B,ndet) int32, det_count (B) int32 (slots >= det_count[i] are padding: never
+ * read) and r = radius_factor * double(scale[i]):
+ *   - no detection of class `category` among the det_count[i] real ones: sel[i] = -1, radius_raw[i] = r, and box / center / radius are
+ *     captra_crop_box's bit for bit;
+ *   - otherwise repeat: box = captra_crop_box's projection of (center, r) (the 0.05 clamp inside the projection only); IoU of that box
+ *     with every detection box -- intersection and the three areas as 64-bit integers max(x2 - x1, 0) * max(y2 - y1, 0), ONE float64
+ *     division, times (class == category); stop when the largest IoU > 0.05 or r > 0.5, else r *= 1.2 (float64).  sel[i] = the FIRST
+ *     arg max of the last round's IoUs (after a give-up with every IoU zero: detection 0, whatever its class, as in the reference),
+ *     box = the last round's box, radius_raw[i] = the grown r (what the reference hands on to the crop), radius[i] = max(r, 0.05) (what
+ *     captra_crop_ball reads).
+ * Outside the reference's contract: a detection whose union with the box is 0 counts as IoU 0 (the reference divides 0 by 0); a growth
+ * step that does not enlarge r (r not finite, r <= 0, or a subnormal that 1.2 x rounds back to itself) ends the loop at once with that
+ * round's selection (the reference would not terminate).  Box coordinates are taken to be image-sized (|coordinate| < 2^30).
+ * Any ndet >= 0: one wave per trajectory strides over the detections. */
+int captra_crop_box_det(int b, int h, int w, int ndet, int category, double radius_factor, const float *trans, const float *scale,
+                        const double *kmat, const int *det_boxes, const int *det_class, const int *det_count, int *box, double *center,
+                        double *radius, double *radius_raw, int *sel, captra_stream_t stream);
+/* captra_crop_ball with the instance mask of trajectory i read from det_masks (B,ndet,h,w) bytes at detection sel[i]; where sel[i] < 0
+ * (or >= ndet) from mask (B,h,w), as captra_crop_ball does. */
+int captra_crop_ball_det(int b, int h, int w, int cap, int ndet, const int *depth, const unsigned char *mask,
+                         const unsigned char *det_masks, const int *sel, const int *box, const double *center, const double *radius,
+                         const double *kinv, double *pts, unsigned char *obj, int *pix, int *counts, captra_stream_t stream);
 /* The rest of the re-crop without the host (csrc/crop.hip; reference nocs_data_process.py:92-109, 43-50, 227-236): the candidate
  * lists of the crops (member table repeated until >= num_points entries) as the sampler's fp32 input with their lengths, from the
  * DEVICE-resident member counts of captra_crop_ball -- cand (B,stride,3), lens (B,) for captra_fps_gather_ragged, info[4] (zeroed

@@ -3,6 +3,8 @@ trajectories, one sampling launch per trajectory (the reference's structure) vs 
 and without the spatially pruned sampler.
 
 Usage: python tools/bench_otf.py [--batch 32]
+       python tools/bench_otf.py --detections [K]     the detector route (`--track_cfg/nocs2d_label True`) against the pre-fetched mask:
+                                                      the re-crop stage and the 32-trajectory step, both in one process
 """
 from __future__ import annotations
 
@@ -146,7 +148,62 @@ def objects_loop(n_objects: int, batch: int = 32, frames: int = 8, loops: int = 
     print(f"{n_objects} objects: min {min(out):.2f}  max {max(out):.2f} ms per step")
 
 
+def detections_leg(batch: int = 32, num_det: int = 8, frames: int = 8, iters: int = 20):
+    """With and without detections, in ONE process: the re-crop stage (sync-free form, device-event time per call) and the otf step of
+    `batch` trajectories (EvalTrackModel loop with nocs2d_label set: eager steps, single batch -- the captured step and the two lanes are
+    excluded for that flag either way)."""
+    from captra_amd.configs import make_config
+    from captra_amd.synthetic import make_otf_detections, make_state_dict
+    from captra_amd.trainer import Trainer
+    dev = torch.device("cuda:0")
+    data = make_otf_detections(batch, frames, seed=1, num_det=num_det)
+    pre = {k: v.to(dev) for k, v in data[1]["meta"]["pre_fetched"].items()}
+    pose = data[0]["meta"]["nocs2camera"][0]
+    trans, scale = pose["translation"].reshape(batch, 3).float().to(dev), pose["scale"].reshape(batch).float().to(dev)
+    gt = {k: pose[k].double().numpy().reshape((batch,) + s) for k, s in (("rotation", (3, 3)), ("translation", (3,)), ("scale", ()))}
+    det = {k: pre[k] for k in nocs_otf.DET_KEYS}
+    det["category"] = 1
+    for label, d in (("pre-fetched mask", None), (f"detector route, K = {num_det}", det)):
+        def stage():
+            return nocs_otf.full_data_batch_arrays(pre["depth"], pre["mask"], None, None, gt, 4096, pose_dev=(trans, scale, 0.6), defer=5 * 4096, det=d)
+        for _ in range(3):
+            stage()
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(iters):
+            stage()
+        ev[1].record()
+        torch.cuda.synchronize()
+        print(f"re-crop stage, {label:28s} {ev[0].elapsed_time(ev[1]) / iters:7.3f} ms per step of {batch} trajectories (sync-free form, device events)", flush=True)
+    for f in data:
+        f["meta"]["pre_fetched"] = {k: v.to(dev) for k, v in f["meta"]["pre_fetched"].items()}
+    for label, with_det in (("pre-fetched mask", False), (f"detector route, K = {num_det}", True)):
+        cfg = make_config("1", experiment_dir="/tmp/captra_otf_bench", nocs_otf=True, **{"init_frame/gt": True})
+        cfg["device"] = dev
+        cfg["track_cfg"]["nocs2d_label"] = True
+        trainer = Trainer(cfg)
+        trainer.model.load_state_dict(make_state_dict({k: tuple(v.shape) for k, v in trainer.model.state_dict().items()}, seed=7))
+        frames_in = data if with_det else [{**f, "meta": {**f["meta"], "pre_fetched": {k: f["meta"]["pre_fetched"][k] for k in ("depth", "mask")}}} for f in data]
+        np.random.seed(0)
+        ts = []
+        for rep in range(4):
+            trainer.model.eval()
+            trainer.model.set_data(frames_in)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            trainer.model.test(save=False, no_eval=True)
+            torch.cuda.synchronize()
+            if rep:
+                ts.append((time.perf_counter() - t0) / (frames - 1))
+        print(f"otf step, nocs2d_label, {label:28s} {1e3 * sorted(ts)[len(ts) // 2]:7.2f} ms per step of {batch} trajectories (median of 3 loops; all: {[round(1e3 * t, 2) for t in ts]})", flush=True)
+
+
 if __name__ == "__main__":
+    if "--detections" in sys.argv:
+        i = sys.argv.index("--detections")
+        detections_leg(num_det=int(sys.argv[i + 1]) if len(sys.argv) > i + 1 and sys.argv[i + 1].isdigit() else 8)
+        sys.exit(0)
     if "--objects" in sys.argv:
         objects_loop(int(sys.argv[sys.argv.index("--objects") + 1]))
         sys.exit(0)
