@@ -231,12 +231,13 @@ __global__ __launch_bounds__(256) void otf_candidates_kernel(int cap, int stride
                                                              int *__restrict__ lens, int *__restrict__ info) {
     const int b = blockIdx.y;
     const int c = counts[b * 2];
-    const int cc = c < 1 ? 1 : (c > stride ? stride : c);           // rare rows clamped: every access stays inside its buffer
+    const int lim = cap < stride ? cap : stride;                    // members a list may name: what the table holds, at most a stride
+    const int cc = c < 1 ? 1 : (c > lim ? lim : c);                 // rare rows clamped: every access stays inside its instance's table
     const int len = otf_list_length(cc, num_points);
     const int keep = len < stride ? len : stride;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         lens[b] = keep;
-        if (c < 10 || c > stride || len > stride) atomicOr(info, 1);
+        if (c < 10 || c > lim || len > stride) atomicOr(info, 1);
         atomicMax(info + 1, c > cap ? cap : otf_list_length(c < 1 ? 1 : c, num_points));
     }
     const double *pb = pts + (size_t)b * cap * 3;
@@ -260,7 +261,8 @@ __global__ __launch_bounds__(256) void otf_finish_kernel(int cap, int stride, in
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int c = counts[b * 2];
-    const int cc = c < 1 ? 1 : (c > stride ? stride : c);
+    const int lim = cap < stride ? cap : stride;
+    const int cc = c < 1 ? 1 : (c > lim ? lim : c);                   // otf_candidates_kernel's clamp
     const int m = picks[(size_t)b * n + i] % cc;                      // candidate -> member
     const double *q = pts + ((size_t)b * cap + m) * 3;
     const bool o = obj[(size_t)b * cap + m] != 0;
@@ -322,7 +324,8 @@ extern "C" int captra_crop_ball_det(int b, int h, int w, int cap, int ndet, cons
 
 // The candidate lists of a re-crop and the ragged sampler's per-cloud counts, from the crop's device-resident member counts (see the
 // kernels above).  cand (B,stride,3) fp32, lens (B,), info: 4 ints, zeroed here on the stream, [0] = a rare-path instance was met
-// (< 10 members, or a list longer than `stride`), [1] = the longest list.  num_points <= stride.
+// (< 10 members, more members than `stride` or than the table's `cap` rows, or a list longer than `stride`), [1] = the longest list.
+// num_points <= stride; cap may be smaller than stride (a list then repeats the first cap members: it never leaves its table).
 extern "C" int captra_otf_candidates(int b, int cap, int stride, int num_points, const double *pts, const int *counts, float *cand,
                                      int *lens, int *info, captra_stream_t stream) {
     if (b < 0 || cap < 1 || stride < 1 || num_points < 1 || num_points > stride) return -1;

@@ -457,7 +457,10 @@ int captra_crop_ball_det(int b, int h, int w, int cap, int ndet, const int *dept
  * lists of the crops (member table repeated until >= num_points entries) as the sampler's fp32 input with their lengths, from the
  * DEVICE-resident member counts of captra_crop_ball -- cand (B,stride,3), lens (B,) for captra_fps_gather_ragged, info[4] (zeroed
  * by the call): [0] != 0 when an instance is on a rare path (< 10 members: the crop's radius grows; a list longer than stride <= 5
- * num_points: thinning by the host's generator) whose frame the caller runs again with the host in the loop, [1] = longest list --
+ * num_points: thinning by the host's generator; more members than stride or than the cap rows its table holds) whose frame the caller
+ * runs again with the host in the loop, [1] = longest list (cap for a count beyond the table).  Both calls clamp a count to
+ * [1, min(cap, stride)] before they index the table, so any cap >= 1 is allowed, below stride as well: a rare row's list repeats the
+ * members the table holds and a pick is reduced modulo that clamped count --
  * and the sampler's picks turned into the frame's tensors in the networks' layouts: points - mean (B,3,n) fp32, labels (B,n)
  * int64, ground-truth NOCS (B,3,n) fp32 of the object's points (float64 arithmetic, rot (B,3,3), trans (B,3), scale (B,) float64). */
 int captra_otf_candidates(int b, int cap, int stride, int num_points, const double *pts, const int *counts, float *cand, int *lens,
