@@ -161,6 +161,66 @@ __device__ void rs_umeyama(const double M[9], const double C6[6], const double s
     *sc_out = sca;
 }
 
+// The SOLVER of rs_fit: what turns the centred moments of a set of pairs (three members, or the winner's inliers) into a pose.
+// RsUmeyama is the similarity fit above (rotation, scale, translation all free).
+struct RsUmeyama {
+    __device__ __forceinline__ void operator()(const double M[9], const double C6[6], const double sb[3], const double tb[3], double R[9],
+                                               double *sc_out, double tr[3]) const {
+        rs_umeyama(M, C6, sb, tb, R, sc_out, tr);
+    }
+};
+
+// RsGivenRot: the rotation R0 is GIVEN (the workgroup's), scale and translation are fitted -- the algebra of part_fit_st_kernel
+// (pose_fit.hip) on the same moments: SYM finds the in-plane rotation about y from the (x,z) block of R0^T M by atan2 (h = 0: identity;
+// a NaN propagates) and R = R0 embed_y; s = <R, M> / (<R^T R, Css> + 1e-6), honouring a non-orthonormal R; t = tb - s R sb.
+template <bool SYM>
+struct RsGivenRot {
+    double R0[9];
+    __device__ void operator()(const double M[9], const double C6[6], const double sb[3], const double tb[3], double R[9], double *sc_out,
+                               double tr[3]) const {
+        for (int i = 0; i < 9; ++i) R[i] = R0[i];
+        if constexpr (SYM) {
+            double M2[4];
+            const int ax[2] = {0, 2};
+            for (int i = 0; i < 2; ++i)
+                for (int j = 0; j < 2; ++j) {
+                    double acc = 0;
+                    for (int k = 0; k < 3; ++k) acc += R0[k * 3 + ax[i]] * M[k * 3 + ax[j]];
+                    M2[i * 2 + j] = acc;
+                }
+            const double a = M2[0] + M2[3], c = M2[2] - M2[1];
+            const double h = sqrt(a * a + c * c);
+            double cs = 1.0, sn = 0.0;
+            if (h > 0.0) {
+                cs = a / h;
+                sn = c / h;
+            } else if (h != h) {
+                cs = sn = NAN;
+            }
+            const double R3[9] = {cs, 0, -sn, 0, 1, 0, sn, 0, cs};
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    double acc = 0;
+                    for (int k = 0; k < 3; ++k) acc += R0[i * 3 + k] * R3[k * 3 + j];
+                    R[i * 3 + j] = acc;
+                }
+        }
+        double num = 0;
+        for (int i = 0; i < 9; ++i) num += R[i] * M[i];
+        const double Css[9] = {C6[0], C6[1], C6[2], C6[1], C6[3], C6[4], C6[2], C6[4], C6[5]};
+        double dn = 0;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                double g = 0;
+                for (int k = 0; k < 3; ++k) g += R[k * 3 + i] * R[k * 3 + j];
+                dn += g * Css[i * 3 + j];
+            }
+        const double sca = num / (dn + 1e-6);
+        for (int a = 0; a < 3; ++a) tr[a] = tb[a] - sca * (R[a * 3] * sb[0] + R[a * 3 + 1] * sb[1] + R[a * 3 + 2] * sb[2]);
+        *sc_out = sca;
+    }
+};
+
 // What rs_fit found: best / ninl are uniform over the workgroup, ok and the pose are thread 0's (identity / 1 / 0 when not ok).
 struct RsResult {
     int best = 0, ninl = 0;
@@ -172,11 +232,13 @@ struct RsResult {
 // samples_out rows), key_b = the trajectory's index in the draw key.  Every thread of the workgroup calls it (barriers inside);
 // with count < 3 nothing is drawn or scored.  SYM: a hypothesis is scored, and the winner's inliers are selected, by the axis-only
 // test (pose_solve.h) on (fp32 second column of R_h, fp32 s_h, fp32 t_h) -- seven floats in the same twelve-float slot; draws,
-// hypotheses, work items, first best, the refit and the validity rule are the same code.
-template <bool SYM>
+// hypotheses, work items, first best, the refit and the validity rule are the same code.  Solver: what fits a pose to a set of pairs,
+// a compile-time policy used for the hypotheses and for the refit alike (RsUmeyama: the similarity fit; RsGivenRot: scale and
+// translation under the workgroup's rotation, captra_part_fit_st_ransac).
+template <bool SYM, class Solver = RsUmeyama>
 __device__ __forceinline__ void rs_fit(const RsMembers &mem, int count, int q, int key_b, int pi, int num_hyps, float th,
                                        const int *__restrict__ sample_rank, unsigned long long seed, int *__restrict__ samples_out,
-                                       RsLds &L, RsResult &res) {
+                                       RsLds &L, RsResult &res, const Solver &solve = Solver()) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned short *idx = mem.idx;
     if (tid < RS_MAX_H) L.score[tid] = 0;
@@ -228,7 +290,7 @@ __device__ __forceinline__ void rs_fit(const RsMembers &mem, int count, int q, i
                 C6[3] += sc[1] * sc[1]; C6[4] += sc[1] * sc[2]; C6[5] += sc[2] * sc[2];
             }
             double R[9], sca, tr[3];
-            rs_umeyama(M, C6, sb, tb, R, &sca, tr);
+            solve(M, C6, sb, tb, R, &sca, tr);
             if constexpr (SYM) {
                 for (int a = 0; a < 3; ++a) L.hp[h * 12 + a] = (float)R[a * 3 + 1];
                 L.hp[h * 12 + 3] = (float)sca;
@@ -332,7 +394,7 @@ __device__ __forceinline__ void rs_fit(const RsMembers &mem, int count, int q, i
             rs_block_sum<15>(r2, L.red);
             if (tid == 0) {
                 double R[9], sca, tr[3];
-                rs_umeyama(r2, r2 + 9, sb, tb, R, &sca, tr);
+                solve(r2, r2 + 9, sb, tb, R, &sca, tr);
                 float fR[9], fs = (float)sca, ft[3] = {(float)tr[0], (float)tr[1], (float)tr[2]};
                 float chk = fs + ((ft[0] + ft[1]) + ft[2]);
                 for (int i = 0; i < 9; ++i) {

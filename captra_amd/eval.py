@@ -95,6 +95,27 @@ def guard_test_name(data: dict) -> str:
     return "axis-only" if head is not None and bool(np.all(head.get("yaxis_only", False))) else "full-rotation"
 
 
+def st_fit_table(name: str, data: dict) -> list:
+    """The robust scale / translation fit's record of one result pickle (present when the run had track_cfg/st_fit/ransac): one line
+    per part with the frames whose fit was kept / replaced by the previous value, and over the frames kept the mean number of
+    inliers -- as a fraction of the part's members where the pickle also carries the guard's record (its `count`: the frame record
+    of the fit itself is two integers, inliers and valid)."""
+    frames = [(i, np.asarray(r["valid"]).reshape(-1), np.asarray(r["inliers"]).reshape(-1)) for i, r in enumerate(data["st_fit"])
+              if r is not None and "valid" in r]
+    guard = data.get("guard")
+    lines = []
+    for p in range(len(frames[0][1]) if frames else 0):
+        kept = [(i, int(n[p])) for i, v, n in frames if int(v[p]) != 0]
+        held = [str(i) for i, v, _ in frames if int(v[p]) == 0]
+        col = f"mean inliers {np.mean([n for _, n in kept]):.1f}" if kept else "mean inliers -"
+        if kept and guard is not None and all(guard[i] is not None and "count" in guard[i] for i, _ in kept):
+            frac = [n / max(int(np.asarray(guard[i]["count"]).reshape(-1)[p]), 1) for i, n in kept]
+            col += f", mean inlier fraction {np.mean(frac):.3f}"
+        lines.append(f"{name} part {p}: kept {len(kept)}; previous value {len(held)}" + (f" [{' '.join(held)}]" if held else "")
+                     + f"; {col} (of {len(frames)} frames)")
+    return lines
+
+
 def write_csv(errors: dict, path: str) -> None:
     keys = list(next(iter(errors.values())).keys())
     with open(path, "w") as f:
@@ -120,7 +141,7 @@ def main(argv=None) -> dict:
     del args.eval_device
     cfg = get_config(args, save=False)
     data_path = pjoin(cfg["experiment_dir"], "results", "data")
-    errors, guard_lines, guard_tests = {}, [], set()
+    errors, guard_lines, guard_tests, st_lines = {}, [], set(), []
     for raw in sorted(os.listdir(data_path)):
         with open(pjoin(data_path, raw), "rb") as f:
             data = pickle.load(f)
@@ -128,6 +149,8 @@ def main(argv=None) -> dict:
         if "guard" in data:
             guard_lines += guard_table(raw.rsplit(".", 1)[0], data)
             guard_tests.add(guard_test_name(data))
+        if "st_fit" in data:
+            st_lines += st_fit_table(raw.rsplit(".", 1)[0], data)
     if not errors:
         raise SystemExit(f"no result pickles under {data_path}")
     err_path = pjoin(cfg["experiment_dir"], "results", "err.pkl")
@@ -140,6 +163,10 @@ def main(argv=None) -> dict:
     if guard_lines:
         print(f"track guard ({' / '.join(sorted(guard_tests))} inlier test), frames per trajectory and part:")
         for line in guard_lines:
+            print("  " + line)
+    if st_lines:
+        print("robust scale / translation fit (track_cfg/st_fit), frames per trajectory and part:")
+        for line in st_lines:
             print("  " + line)
     return avg
 

@@ -266,7 +266,7 @@ class TrackLanes:
                 pairs = [(out[k], self.ring[slot][k][s]) for k in out] + [(out[k], g.pose[k]) for k in out]
                 if self.npcs_ring is not None:
                     pairs += [(g.npcs_pred[k], dst[s]) for k, dst in self.npcs_ring[slot].items()]
-                fused.copy_multi(pairs)                  # (6 pose + 3 map jobs, 4 more with a guard record: within the launch's 16)
+                fused.copy_multi(pairs)                  # (6 pose + 3 map jobs, 4 more with a guard record, 2 with the robust fit's: 15, within the launch's 16)
                 self.written[slot][l].record(st)
         return slot
 

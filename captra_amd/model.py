@@ -113,6 +113,7 @@ def _frame_names(frame):
 # reference's preprocessing uses 1 mm on rendered (exact) maps (align_pose.py:49), sensor depth at 1 m is noisy at the millimetre
 INIT_FIT_INLIER_TH = 0.005
 GUARD_KEYS = ("count", "inliers", "rms", "verdict")     # a frame's guard record: (B,P) tensors (pose_utils/pose_fit.py)
+ST_FIT_KEYS = ("inliers", "valid")                      # a frame's record of the robust scale / translation fit: (B,P) int32 tensors
 
 
 class EvalTrackModel(BaseModel):
@@ -139,6 +140,11 @@ class EvalTrackModel(BaseModel):
         # by the first-pose estimator.  Absent: no launch, no tensor, no pickle entry.
         self.guard = self._guard_cfg(cfg)
         self._warn_full_rotation_test(cfg)
+        # track_cfg: {st_fit: {ransac: True, ...}}: every step's scale / translation by RANSAC with RotationNet's rotation given
+        # (csrc/pose_st_ransac.hip, in place of the one-pass fit's launch, captured with the step); the inlier test is the axis-only
+        # one for a symmetric category.  The guard, when on, judges the pose this fit produced.  Absent / ransac: False: nothing
+        # is launched, no tensor, no pickle entry.
+        self.st_fit = self.net.st_fit = self._st_fit_cfg(cfg)
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
         self.radius = cfg["data_radius"]
         self.det_category = cfg["obj_category"]          # nocs2d_label: the class id the frame's detections are matched against
@@ -200,6 +206,27 @@ class EvalTrackModel(BaseModel):
         if EvalTrackModel._yaxis_only(cfg, g, "track_cfg/guard/yaxis_only"):
             out["yaxis_only"] = True            # (carried only when on)
         return out
+
+    @staticmethod
+    def _st_fit_cfg(cfg):
+        """track_cfg/st_fit, parsed once: None when absent or ransac is not set; inlier_th is a fraction of data_radius (the guard's
+        default), num_hyps and seed default to init_frame's, as the guard's do."""
+        s = cfg["track_cfg"].get("st_fit")
+        if s is None or not s.get("ransac", False):
+            return None
+        frac = s.get("inlier_th")
+        frac = INIT_FIT_INLIER_TH if frac is None else float(frac)
+        num_hyps = s.get("num_hyps")
+        num_hyps = int(cfg["init_frame"].get("num_hyps", 64) if num_hyps is None else num_hyps)
+        seed = s.get("seed")
+        seed = int(cfg["init_frame"].get("seed", 0) if seed is None else seed)
+        if not (frac > 0.0 and np.isfinite(frac)):
+            raise ValueError(f"track_cfg/st_fit/inlier_th must be a positive fraction of data_radius, got {s.get('inlier_th')!r}")
+        if not 1 <= num_hyps <= 256:
+            raise ValueError(f"track_cfg/st_fit/num_hyps must be in [1, 256] (the kernel's limit), got {num_hyps}")
+        if seed < 0:
+            raise ValueError(f"track_cfg/st_fit/seed must not be negative, got {seed}")
+        return {"inlier_th": frac * float(cfg["data_radius"]), "num_hyps": num_hyps, "seed": seed}
 
     @staticmethod
     def _yaxis_only(cfg, section, name) -> bool:
@@ -423,7 +450,12 @@ class EvalTrackModel(BaseModel):
         input.pop("shared_geometry", None)
         if self.share_geometry and self.num_parts == 1 and not self.npcs_net.training:
             input["shared_geometry"] = (self.npcs_net.last_canon, self.npcs_net.backbone.last_geom)
-        pose = self.net(input, test_mode=True)["part"]
+        out = self.net(input, test_mode=True)
+        pose = out["part"]
+        if self.st_fit is not None:
+            # the robust fit's record joins CoordinateNet's maps (`st_*`), so it travels with them through every batch form
+            for k in ST_FIT_KEYS:
+                npcs_pred["st_" + k] = out["st_fit"][k]
         return pose if self.guard is None else self._guard_step(input, npcs_pred, pose)
 
     def _guard_step(self, input, npcs_pred, pose):
@@ -731,6 +763,7 @@ class EvalTrackModel(BaseModel):
         feed = self.feed_dict
         pred_poses, npcs_pred = [self._initial_pose()], [None]
         guard = {}                          # frame -> its guard record (guard on)
+        st_fit = {}                         # frame -> the robust fit's record (track_cfg/st_fit on)
         if self.frame_hook is not None:
             self.frame_hook(0, pred_poses[0])
         self.timer.tick()
@@ -744,7 +777,9 @@ class EvalTrackModel(BaseModel):
             with torch.no_grad():
                 run_frame, commit, poses, bounds, join = frames(pred_poses[0])
                 if self.guard is not None:
-                    commit = self._commit_with_guard(commit, guard)
+                    commit = self._commit_with_record(commit, guard, "guard_", GUARD_KEYS)
+                if self.st_fit is not None:
+                    commit = self._commit_with_record(commit, st_fit, "st_", ST_FIT_KEYS)
                 pending = None                  # (frame, poses that entered it, its deferred checks)
 
                 def settle():
@@ -784,16 +819,19 @@ class EvalTrackModel(BaseModel):
         self.pred_dict = {"poses": pred_poses, "npcs_pred": npcs_pred}
         if self.guard is not None:
             self.pred_dict["guard"] = [None] + [guard[i] for i in range(1, len(feed))]
+        if self.st_fit is not None:
+            self.pred_dict["st_fit"] = [None] + [st_fit[i] for i in range(1, len(feed))]
         self.check_l1_stream()
         if save:
             self._save(list(map(_frame_names, feed)))
 
     @staticmethod
-    def _commit_with_guard(commit, records):
-        """`commit` of a batch form, with the frame's guard record taken out of CoordinateNet's maps into records[frame]."""
+    def _commit_with_record(commit, records, prefix, keys):
+        """`commit` of a batch form, with the frame's record (the guard's `guard_*`, the robust fit's `st_*`) taken out of
+        CoordinateNet's maps into records[frame]."""
         def wrapped(i, result):
             npcs, pose = commit(i, result)
-            records[i] = {k: npcs.pop("guard_" + k) for k in GUARD_KEYS}
+            records[i] = {k: npcs.pop(prefix + k) for k in keys}
             return npcs, pose
         return wrapped
 
@@ -828,6 +866,8 @@ class EvalTrackModel(BaseModel):
                 # which test counted the inliers: one boolean, in the slot of frame 0 (which has no record: None otherwise), only
                 # when on -- the frames' records keep their four keys
                 save_dict["guard"][0] = {"yaxis_only": np.ones(len(self.feed_dict[0]["meta"]["path"]), bool)}
+        if self.st_fit is not None:
+            save_dict["st_fit"] = [None if r is None else {k: v.detach().cpu().numpy() for k, v in r.items()} for r in self.pred_dict["st_fit"]]
         records = []
         for i, path in enumerate(self.feed_dict[0]["meta"]["path"]):
             instance, track_num = path.split(".")[-2].split("/")[-3:-1]

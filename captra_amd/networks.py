@@ -17,7 +17,7 @@ from .backbones import PointNet2Msg
 from .blocks import RotationRegressor, get_point_mlp, run_point_mlp
 from .fold import fold_conv_bn
 from .pose_utils.part_dof_utils import convert_pred_rtvec_to_matrix, merge_reenact_canon_part_pose
-from .pose_utils.pose_fit import part_fit_st_cn, part_fit_st_track
+from .pose_utils.pose_fit import part_fit_st_cn, part_fit_st_ransac_track, part_fit_st_track
 from .pose_utils.procrustes import (rot_around_yaxis_to_3d, scale_pts_mask, transform_pts_2d_mask,
                                     translate_pts_mask)
 
@@ -219,11 +219,25 @@ class PartCanonNet(nn.Module):
         self.root = [i for i in range(self.num_parts) if self.tree[i] == -1][0]
         self.cfg = cfg
         self.return_point_rotation = False
+        # the ROBUST scale / translation fit of the tracking step (captra_part_fit_st_ransac): None = the one-pass fit, as ever;
+        # {'inlier_th', 'num_hyps', 'seed'} (EvalTrackModel sets it from track_cfg/st_fit) = RANSAC with this net's rotation given
+        self.st_fit = None
+
+    def _robust_fit(self, input, labels_i32, npcs, rotation, part_pose):
+        """test_mode with `st_fit` set: the step's scale / translation by the robust fit; an invalid fit keeps the previous values
+        inside the launch.  input['b0']: the first trajectory's index within the whole batch (the kernel's draws).
+        -> (pose, the frame's record {'inliers', 'valid'}: (B,P) int32)."""
+        st = self.st_fit
+        scale, trans, valid, info = part_fit_st_ransac_track(labels_i32, npcs, input["points"].float().contiguous(), input["points_mean"],
+                                                             rotation, part_pose["scale"], part_pose["translation"], self.sym,
+                                                             st["inlier_th"], num_hyps=st["num_hyps"], seed=st["seed"],
+                                                             b0=int(input.get("b0", 0)))
+        return {"rotation": rotation, "scale": scale, "translation": trans}, {"inliers": info["inliers"], "valid": valid.int()}
 
     def forward(self, input, test_mode=False):
         """input: {'points' (B,3,N), 'points_mean' (B,3,1), 'state': {'part': pose}, 'pred_labels',
         'pred_nocs' (B,P,3,N), ...} -> {'part': {'rotation' (B,P,3,3), 'scale' (B,P),
-        'translation' (B,P,3,1)}, 'point_rotation' (B,P,N,3,3)}."""
+        'translation' (B,P,3,1)}, 'point_rotation' (B,P,N,3,3)[, 'st_fit': the robust fit's record (test_mode with `st_fit` set)]}."""
         part_pose = input["state"]["part"]
         P = self.num_parts
         if "canon_pose" in input:
@@ -257,6 +271,9 @@ class PartCanonNet(nn.Module):
                 labels_i32 = input["pred_labels"].int().contiguous()
             rotation = fused.rot_pool_compose(raw, labels_i32, part_pose["rotation"].float().contiguous(), self.sym)
             npcs = input["pred_nocs"].reshape(B, P, 3, -1).float().contiguous()
+            if self.st_fit is not None:
+                pose, record = self._robust_fit(input, labels_i32, npcs, rotation, part_pose)
+                return {"part": pose, "st_fit": record}
             # camera points = points + mean and "an invalid fit keeps the previous scale / translation" inside the launch
             scale, trans, _ = part_fit_st_track(labels_i32, npcs, input["points"].float().contiguous(), input["points_mean"], rotation,
                                                 part_pose["scale"], part_pose["translation"], self.sym)
@@ -283,6 +300,13 @@ class PartCanonNet(nn.Module):
             labels = input["pred_labels"] if test_mode else input["labels"]
             fit_rot = rotation if test_mode else input["gt_part"]["rotation"]
             npcs = input["pred_nocs"].reshape(B, P, 3, -1).float().contiguous()
+            if test_mode and self.st_fit is not None:
+                # (no `where` below: the kernel keeps the previous values of an invalid fit)
+                final_pose, record = self._robust_fit(input, labels.int().contiguous(), npcs, rotation.float().contiguous(), part_pose)
+                ret = {"part": final_pose, "st_fit": record}
+                if "point_rotation" in out:
+                    ret["point_rotation"] = out["point_rotation"]
+                return ret
             cam_points = (input["points"] + input["points_mean"]).float().contiguous()        # (B,3,N)
             scale, trans, valid = part_fit_st_cn(labels.int().contiguous(), npcs, cam_points,
                                                  fit_rot.float().contiguous(), self.sym)

@@ -29,6 +29,9 @@ _FLAGS = [  # (name, type, default)
     # the axis-only inlier test of the symmetric categories, in the guard and in the first-pose fit (init_frame/fit).  Not given = not
     # in the namespace at all (argparse.SUPPRESS): the key reaches the configuration only when it was written
     ("track_cfg/guard/yaxis_only", boolean_string, argparse.SUPPRESS), ("init_frame/yaxis_only", boolean_string, argparse.SUPPRESS),
+    # the robust scale / translation fit of every step (model.py: EvalTrackModel.st_fit); off unless ransac is True
+    ("track_cfg/st_fit/ransac", boolean_string, None), ("track_cfg/st_fit/inlier_th", float, None), ("track_cfg/st_fit/num_hyps", int, None),
+    ("track_cfg/st_fit/seed", int, None),
     # optimisation
     ("total_epoch", int, None), ("optimizer", str, None), ("weight_decay", float, None), ("learning_rate", float, None),
     ("lr_policy", str, None), ("lr_gamma", float, None), ("lr_step_size", int, None), ("lr_clip", float, None), ("freq/save", int, None),

@@ -114,6 +114,59 @@ def part_fit_ransac(labels, source, target, cfg, num_hyps=64, inlier_th=1e-3, sa
     return {"rotation": rot, "scale": scale, "translation": trans}, valid, info
 
 
+def _part_fit_st_ransac_call(labels_i32, src_cn, tgt_cn, tgt_per_part, tgt_mean, rotation, prev_scale, prev_trans, sym, inlier_th,
+                             num_hyps, seed, b0, sample_rank):
+    """captra_part_fit_st_ransac on prepared tensors -> scale (B,P), trans (B,P,3), valid (B,P) int32, inliers, best (B,P) int32."""
+    B, P, _, N = src_cn.shape
+    dev = src_cn.device
+    if sample_rank is not None:
+        sample_rank = sample_rank.reshape(B, P, int(num_hyps), 3).int().contiguous()
+    L.require_device(labels_i32, src_cn, tgt_cn, tgt_mean, rotation, prev_scale, prev_trans, sample_rank)
+    scale = torch.empty(B, P, dtype=torch.float32, device=dev)
+    trans = torch.empty(B, P, 3, dtype=torch.float32, device=dev)
+    valid = torch.empty(B, P, dtype=torch.int32, device=dev)
+    best = torch.empty(B, P, dtype=torch.int32, device=dev)
+    ninl = torch.empty(B, P, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("captra_part_fit_st_ransac", B, P, N, 1 if sym else 0, int(b0), int(num_hyps), float(inlier_th), L.ptr(labels_i32),
+               L.ptr(src_cn), L.ptr(tgt_cn), 1 if tgt_per_part else 0, L.ptr(tgt_mean), L.ptr(rotation), L.ptr(prev_scale),
+               L.ptr(prev_trans), L.ptr(sample_rank), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(scale), L.ptr(trans), L.ptr(valid),
+               L.ptr(best), L.ptr(ninl))
+    return scale, trans, valid, ninl, best
+
+
+def part_fit_st_ransac_track(labels_i32, src_cn, pts_cn, pts_mean, rotation, prev_scale, prev_trans, sym: bool, inlier_th,
+                             num_hyps=64, seed=0, b0=0, sample_rank=None):
+    """The track loop's ROBUST fit in one launch (captra_part_fit_st_ransac, include/captra_hip.h): part_fit_st_track's arguments --
+    target = pts (B,3,N) + pts_mean (B,3,1) formed inside the kernel, invalid fits keep prev_scale (B,P) / prev_trans (B,P,3,1) --
+    plus the inlier distance, the number of three-member hypotheses, the seed of the kernel's draws with b0 = the index of the first
+    trajectory within the whole batch (or sample_rank (B,P,H,3) int32 member ranks)
+    -> scale (B,P), translation (B,P,3,1), valid (B,P) bool, info {'inliers', 'best' (B,P) int32}."""
+    B, P, _, N = src_cn.shape
+    pts_mean = pts_mean.reshape(B, 3).float().contiguous()
+    prev_scale = prev_scale.float().contiguous()
+    prev_trans = prev_trans.reshape(B, P, 3).float().contiguous()
+    scale, trans, valid, ninl, best = _part_fit_st_ransac_call(labels_i32, src_cn, pts_cn, False, pts_mean, rotation, prev_scale, prev_trans,
+                                                               sym, inlier_th, num_hyps, seed, b0, sample_rank)
+    return scale, trans.unsqueeze(-1), valid.bool(), {"inliers": ninl, "best": best}
+
+
+def part_fit_st_ransac(labels, source, target, rotation, cfg, inlier_th=1e-3, num_hyps=64, seed=0, sample_rank=None, target_mean=None):
+    """The counterpart the reference's part_fit_st_no_ransac is named after, with its argument order and return value: labels (B,N);
+    source, target (B,P,N,3); rotation (B,P,3,3); cfg {'num_parts','sym'}
+    -> ({'rotation','scale' (B,P),'translation' (B,P,3,1)}, valid (B,P) bool).  An invalid fit holds 1 / 0."""
+    assert source.shape[1] == int(cfg["num_parts"]), (source.shape, cfg["num_parts"])
+    B = source.shape[0]
+    src_cn = source.transpose(-1, -2).float().contiguous()
+    tgt_cn = target.transpose(-1, -2).float().contiguous()
+    mean = None if target_mean is None else target_mean.reshape(B, 3).float().contiguous()
+    scale, trans, valid, _, _ = _part_fit_st_ransac_call(labels.int().contiguous(), src_cn, tgt_cn, target.dim() == 4, mean,
+                                                         rotation.float().contiguous(), None, None, bool(cfg["sym"]), inlier_th, num_hyps,
+                                                         seed, 0, sample_rank)
+    model = {"rotation": rotation, "scale": scale, "translation": trans.unsqueeze(-1)}
+    return model, filter_model_valid(model, valid.bool())
+
+
 GUARD_VERDICTS = ("ok", "too_few", "lost", "recovered")      # the codes 0..3 of captra_part_fit_guard
 
 

@@ -728,6 +728,35 @@ int captra_part_fit_guard_sym(int b, int p, int n, int b0, const int *labels, co
                               int min_members, int refit, int num_hyps, unsigned long long seed, int *count, int *inliers, float *rms,
                               int *verdict, float *rot_out, float *scale_out, float *trans_out, captra_stream_t stream);
 
+/* Robust scale / translation fit with the rotation GIVEN: the every-frame fit of the track loop (captra_part_fit_st_track) as a RANSAC
+ * -- the counterpart that the name of the reference's part_fit_st_no_ransac promises (its code has none).  One launch, one workgroup
+ * per (b, p); the shape limits of captra_part_fit_ransac (1 <= P <= 8, 1 <= num_hyps <= 256, 1 <= N <= 16384); these, sym outside
+ * {0, 1}, b0 < 0 or b0 > INT_MAX - b return -1 without a launch; b = 0 returns 0.
+ *   labels, src, tgt, tgt_per_part, tgt_mean, sample_rank, members and ranks: exactly as documented for captra_part_fit_ransac.
+ *   rot (B,P,3,3) the given rotation; prev_scale (B,P) / prev_trans (B,P,3) or NULL.
+ *   estimator E(pairs, R, sym), in double -- the algebra of captra_part_fit_st on a set of pairs: centroids sb, tb; the centred
+ *              C = sum tgt_c src_c^T (3x3) and Css = sum src_c src_c^T; sym = 1: M = the (x,z) block of R^T C, a = M00 + M11,
+ *              c = M10 - M01, h = sqrt(a a + c c), (cos, sin) = (a, c) / h (h = 0: (1, 0); a NaN propagates) and
+ *              R' = R [[cos 0 -sin] [0 1 0] [sin 0 cos]]; sym = 0: R' = R;  s = <R', C> / (<R'^T R', Css> + 1e-6);  t = tb - s R' sb.
+ *              No given_scale.
+ *   hypothesis h: E on its three members (sample_rank as it is, or NULL: the draw generator of captra_part_fit_ransac with b0 + b in
+ *              place of b in the key, as in captra_part_fit_guard, so that a lane of a batch draws what the whole batch draws).  Its
+ *              parameters rounded to fp32: sym = 0 (fp32(s R'_ij), fp32(t)); sym = 1 (a = the second column of rot as stored -- R'
+ *              has R's second column, so the score does not depend on the hypothesis's in-plane angle; its t does --, fp32(s), fp32(t)).
+ *   score(h):  sym = 0 the inlier test of captra_part_fit_ransac, sym = 1 the axis-only test of captra_part_fit_ransac_sym, operation
+ *              by operation as defined above; a NaN residual is outside.  best = the FIRST h with the largest score.
+ *   result  :  E on the inliers of best, sums in double in the refit's fixed order, written as fp32.
+ *   -> scale (B,P), trans (B,P,3), valid (B,P) i32 = count > 3 && inliers >= 3 && scale, trans and the sum of rot finite (count > 3
+ *      is captra_part_fit_st's rule: the robust fit does not change which parts count as fitted by size).  An invalid fit writes
+ *      prev_scale / prev_trans, with prev_* NULL 1 / 0: no NaN leaves the kernel when prev_* is finite.  Optional (NULL = not wanted):
+ *      best, num_inliers (B,P) i32: what was found, also for an invalid fit; with count < 3 nothing is drawn and both are 0.
+ * Three-member samples although two pairs determine (s, t) without sym: draws and the sample_rank layout are those of the other two
+ * fits.  Outputs must not alias inputs. */
+int captra_part_fit_st_ransac(int b, int p, int n, int sym, int b0, int num_hyps, float inlier_th, const int *labels, const float *src,
+                              const float *tgt, int tgt_per_part, const float *tgt_mean, const float *rot, const float *prev_scale,
+                              const float *prev_trans, const int *sample_rank, unsigned long long seed, float *scale, float *trans,
+                              int *valid, int *best, int *num_inliers, captra_stream_t stream);
+
 /* CoordinateNet read-out (networks.py:50 F.softmax(dim=1) + model.py:466 torch.max(seg, dim=-2)[1]) in one launch: logits (B,S,N),
  * S <= 8 -> seg (B,S,N) softmax (or NULL), labels (B,N) i32 = FIRST index of the largest logit (or NULL). */
 int captra_seg_softmax_argmax(int b, int s, int n, const float *logits, float *seg, int *labels, captra_stream_t stream);
