@@ -20,6 +20,7 @@
 //   valid = c > 3 and everything finite                                 (pose_fit.py:46, 26-35)
 #include "common.h"
 #include "pose_solve.h"
+#include "rot_pool.h"
 
 #include <math.h>
 
@@ -219,21 +220,6 @@ __global__ __launch_bounds__(PF_THREADS) void procrustes_rot3_kernel(int n, cons
 // Only head p on cloud (b,p) is evaluated (the reference computes all P x P and keeps the diagonal,
 // networks.py:200-203).  The reference runs ~60 tiny ATen kernels for this.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void normalize3(const float v[3], float out[3]) {  // rotations.py:302-314
-    const float mag = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-    if (mag > 1e-8f) {
-        const float d = fmaxf(mag, 1e-8f);
-        out[0] = v[0] / d; out[1] = v[1] / d; out[2] = v[2] / d;
-    } else {
-        out[0] = 1.f; out[1] = 0.f; out[2] = 0.f;
-    }
-}
-__device__ __forceinline__ void cross3(const float u[3], const float v[3], float out[3]) {
-    out[0] = u[1] * v[2] - u[2] * v[1];
-    out[1] = u[2] * v[0] - u[0] * v[2];
-    out[2] = u[0] * v[1] - u[1] * v[0];
-}
-
 __global__ __launch_bounds__(PF_THREADS) void rot_pool_compose_kernel(int p, int n, int sym, int diag, const float *__restrict__ raw,
                                                                       const int *__restrict__ labels,
                                                                       const float *__restrict__ prev_rot,
@@ -241,78 +227,8 @@ __global__ __launch_bounds__(PF_THREADS) void rot_pool_compose_kernel(int p, int
     __shared__ double smem[10 * 4];
     const int q = blockIdx.x;            // = b * P + part: cloud q, head `part`
     const int bi = q / p, pi = q % p;
-    const int R = sym ? 3 : 6;
-    // diag: raw holds only head `part` on cloud (b, part) -- (B*P, R, N); else all P heads per cloud -- (B*P, P, R, N)
-    const float *src = raw + (diag ? (size_t)q : (size_t)q * p + pi) * R * n;
-    const int *lab = labels + (size_t)bi * n;
-    double acc[10];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) acc[i] = 0.0;
-    // (every point is loaded and normalised, a non-member adds +0.0 through a select -- no NaN of a degenerate non-member can
-    // leak in: the loads no longer wait for the label, the loop pipelines, the sums are the same bit for bit)
-#pragma unroll 4
-    for (int e = threadIdx.x; e < n; e += PF_THREADS) {
-        const bool in = lab[e] == pi;
-        acc[9] += in ? 1.0 : 0.0;
-        if (sym) {
-            const float v[3] = {src[e], src[n + e], src[2 * (size_t)n + e]};
-            float u[3];
-            normalize3(v, u);
-            acc[0] += in ? (double)u[0] : 0.0; acc[1] += in ? (double)u[1] : 0.0; acc[2] += in ? (double)u[2] : 0.0;
-        } else {
-            const float a[3] = {src[e], src[n + e], src[2 * (size_t)n + e]};
-            const float c[3] = {src[3 * (size_t)n + e], src[4 * (size_t)n + e], src[5 * (size_t)n + e]};
-            float x[3], zr[3], z[3], y[3];
-            normalize3(a, x);
-            cross3(x, c, zr);
-            normalize3(zr, z);
-            cross3(z, x, y);
-            // row-major 3x3 with columns x, y, z
-            acc[0] += in ? (double)x[0] : 0.0; acc[1] += in ? (double)y[0] : 0.0; acc[2] += in ? (double)z[0] : 0.0;
-            acc[3] += in ? (double)x[1] : 0.0; acc[4] += in ? (double)y[1] : 0.0; acc[5] += in ? (double)z[1] : 0.0;
-            acc[6] += in ? (double)x[2] : 0.0; acc[7] += in ? (double)y[2] : 0.0; acc[8] += in ? (double)z[2] : 0.0;
-        }
-    }
-    block_reduce_sum<10>(acc, smem);
-    if (threadIdx.x != 0) return;
-    const float cnt = (float)acc[9];
-    float dR[9];  // row-major
-    if (sym) {
-        float v[3];
-        if (cnt > 0.f) { v[0] = (float)acc[0] / fmaxf(cnt, 1.f); v[1] = (float)acc[1] / fmaxf(cnt, 1.f); v[2] = (float)acc[2] / fmaxf(cnt, 1.f); }
-        else { v[0] = 0.f; v[1] = 1.f; v[2] = 0.f; }
-        float y[3], zr[3], z[3], x[3];
-        const float ex[3] = {1.f, 0.f, 0.f};
-        normalize3(v, y);
-        cross3(ex, y, zr);
-        normalize3(zr, z);
-        cross3(y, z, x);
-        for (int i = 0; i < 3; ++i) { dR[i * 3 + 0] = x[i]; dR[i * 3 + 1] = y[i]; dR[i * 3 + 2] = z[i]; }
-    } else {
-        float m[9];
-        for (int i = 0; i < 9; ++i) m[i] = cnt > 0.f ? (float)acc[i] / fmaxf(cnt, 1.f) : (i % 4 == 0 ? 1.f : 0.f);
-        // Gram-Schmidt on the columns (rotations.py:356-372)
-        float a1[3] = {m[0], m[3], m[6]}, a2[3] = {m[1], m[4], m[7]}, a3[3] = {m[2], m[5], m[8]};
-        float u2[3], u3[3];
-        auto dot = [](const float *u, const float *v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; };
-        const float k12 = dot(a1, a2) / fmaxf(dot(a1, a1), 1e-8f);
-        for (int i = 0; i < 3; ++i) u2[i] = a2[i] - k12 * a1[i];
-        const float k13 = dot(a1, a3) / fmaxf(dot(a1, a1), 1e-8f);
-        const float k23 = dot(u2, a3) / fmaxf(dot(u2, u2), 1e-8f);
-        for (int i = 0; i < 3; ++i) u3[i] = (a3[i] - k13 * a1[i]) - k23 * u2[i];
-        float c1[3], c2[3], c3[3];
-        normalize3(a1, c1); normalize3(u2, c2); normalize3(u3, c3);
-        for (int i = 0; i < 3; ++i) { dR[i * 3 + 0] = c1[i]; dR[i * 3 + 1] = c2[i]; dR[i * 3 + 2] = c3[i]; }
-    }
-    const float *Rp = prev_rot + (size_t)q * 9;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            float v = 0.f;
-            for (int k = 0; k < 3; ++k) v += Rp[i * 3 + k] * dR[k * 3 + j];
-            rot[(size_t)q * 9 + i * 3 + j] = v;
-        }
-    if (delta != nullptr)
-        for (int i = 0; i < 9; ++i) delta[(size_t)q * 9 + i] = dR[i];
+    // the pooling loop, its reduction and the tail live in rot_pool.h (shared with rot_consensus.hip); here every member pools
+    rp_pool_compose(q, pi, n, sym, rp_head(raw, q, p, pi, n, sym, diag), labels + (size_t)bi * n, prev_rot, rot, delta, smem, RpAllMembers());
 }
 
 }  // namespace

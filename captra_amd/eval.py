@@ -116,6 +116,21 @@ def st_fit_table(name: str, data: dict) -> list:
     return lines
 
 
+def rot_pool_table(name: str, data: dict) -> list:
+    """The consensus rotation read-out's record of one result pickle (present when the run had track_cfg/rot_pool/consensus): one
+    line per part with the frames, over the frames with members the mean and the minimum fraction of the part's votes that were
+    inliers of the winning vote, and the frames without members."""
+    frames = [(i, np.asarray(r["inliers"]).reshape(-1), np.asarray(r["count"]).reshape(-1)) for i, r in enumerate(data["rot_pool"])
+              if r is not None and "count" in r]
+    lines = []
+    for p in range(len(frames[0][1]) if frames else 0):
+        frac = [int(n[p]) / int(c[p]) for _, n, c in frames if int(c[p]) > 0]
+        empty = [str(i) for i, _, c in frames if int(c[p]) == 0]
+        col = f"inlier fraction mean {np.mean(frac):.3f} min {np.min(frac):.3f}" if frac else "inlier fraction -"
+        lines.append(f"{name} part {p}: frames {len(frames)}; {col}; without members {len(empty)}" + (f" [{' '.join(empty)}]" if empty else ""))
+    return lines
+
+
 def write_csv(errors: dict, path: str) -> None:
     keys = list(next(iter(errors.values())).keys())
     with open(path, "w") as f:
@@ -141,7 +156,7 @@ def main(argv=None) -> dict:
     del args.eval_device
     cfg = get_config(args, save=False)
     data_path = pjoin(cfg["experiment_dir"], "results", "data")
-    errors, guard_lines, guard_tests, st_lines = {}, [], set(), []
+    errors, guard_lines, guard_tests, st_lines, rot_lines = {}, [], set(), [], []
     for raw in sorted(os.listdir(data_path)):
         with open(pjoin(data_path, raw), "rb") as f:
             data = pickle.load(f)
@@ -151,6 +166,8 @@ def main(argv=None) -> dict:
             guard_tests.add(guard_test_name(data))
         if "st_fit" in data:
             st_lines += st_fit_table(raw.rsplit(".", 1)[0], data)
+        if "rot_pool" in data:
+            rot_lines += rot_pool_table(raw.rsplit(".", 1)[0], data)
     if not errors:
         raise SystemExit(f"no result pickles under {data_path}")
     err_path = pjoin(cfg["experiment_dir"], "results", "err.pkl")
@@ -167,6 +184,10 @@ def main(argv=None) -> dict:
     if st_lines:
         print("robust scale / translation fit (track_cfg/st_fit), frames per trajectory and part:")
         for line in st_lines:
+            print("  " + line)
+    if rot_lines:
+        print("consensus rotation read-out (track_cfg/rot_pool), per trajectory and part:")
+        for line in rot_lines:
             print("  " + line)
     return avg
 

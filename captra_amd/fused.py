@@ -10,6 +10,7 @@ import ctypes as C
 import os
 import threading
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -967,6 +968,36 @@ def rot_pool_compose(raw, labels_i32, prev_rot, sym: bool, want_delta: bool = Fa
         L.call("captra_rot_pool_compose", B, P, N, 1 if sym else 0, 1 if diag else 0, L.ptr(raw), L.ptr(labels_i32),
                L.ptr(prev_rot), L.ptr(rot), L.ptr(delta))
     return (rot, delta) if want_delta else rot
+
+
+def rot_pool_consensus(raw, labels_i32, prev_rot, sym: bool, angle_th_deg, num_hyps: int = 64, seed: int = 0, b0: int = 0,
+                       sample_rank=None, want_delta: bool = False):
+    """The ROBUST rotation read-out (captra_rot_pool_consensus, include/captra_hip.h): rot_pool_compose's arguments plus the inlier
+    angle in degrees (cos_th = float32(cos(float64 radians)), formed here), the number of one-vote hypotheses, the seed of the
+    kernel's draws with b0 = the index of the first trajectory within the whole batch (or sample_rank (B,P,H) int32 member ranks)
+    -> rotation (B,P,3,3)[, dR], info {'count', 'inliers', 'best'}: (B,P) int32."""
+    B, P = prev_rot.shape[:2]
+    diag = raw.dim() == 3
+    R, N = raw.shape[-2:]
+    if sample_rank is not None:
+        sample_rank = sample_rank.reshape(B, P, int(num_hyps)).int().contiguous()
+    L.require_device(raw, labels_i32, prev_rot, sample_rank)
+    assert raw.shape[0] == B * P and (diag or raw.shape[1] == P) and R == (3 if sym else 6)
+    assert labels_i32.shape == (B, N) and labels_i32.dtype == torch.int32
+    assert prev_rot.shape == (B, P, 3, 3) and raw.is_contiguous() and prev_rot.is_contiguous() and labels_i32.is_contiguous()
+    cos_th = float(np.float32(np.cos(np.deg2rad(np.float64(angle_th_deg)))))
+    dev = raw.device
+    rot = torch.empty(B, P, 3, 3, dtype=torch.float32, device=dev)
+    delta = torch.empty_like(rot) if want_delta else None
+    count = torch.empty(B, P, dtype=torch.int32, device=dev)
+    ninl = torch.empty(B, P, dtype=torch.int32, device=dev)
+    best = torch.empty(B, P, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("captra_rot_pool_consensus", B, P, N, 1 if sym else 0, 1 if diag else 0, int(b0), int(num_hyps), cos_th, L.ptr(raw),
+               L.ptr(labels_i32), L.ptr(prev_rot), L.ptr(sample_rank), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(rot), L.ptr(delta),
+               L.ptr(count), L.ptr(ninl), L.ptr(best))
+    info = {"count": count, "inliers": ninl, "best": best}
+    return (rot, delta, info) if want_delta else (rot, info)
 
 
 USE_GN_FUSED = True      # Conv -> GroupNorm -> ReLU chains: statistics in the conv's epilogue, normalisation in the next conv's load

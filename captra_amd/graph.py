@@ -266,7 +266,10 @@ class TrackLanes:
                 pairs = [(out[k], self.ring[slot][k][s]) for k in out] + [(out[k], g.pose[k]) for k in out]
                 if self.npcs_ring is not None:
                     pairs += [(g.npcs_pred[k], dst[s]) for k, dst in self.npcs_ring[slot].items()]
-                fused.copy_multi(pairs)                  # (6 pose + 3 map jobs, 4 more with a guard record, 2 with the robust fit's: 15, within the launch's 16)
+                # (6 pose + 3 map jobs, 4 more with a guard record, 2 with the robust fit's: 15, within the launch's 16; the consensus
+                # read-out's 2 on top of all of them take a second launch)
+                for j in range(0, len(pairs), 16):
+                    fused.copy_multi(pairs[j:j + 16])
                 self.written[slot][l].record(st)
         return slot
 

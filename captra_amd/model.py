@@ -113,6 +113,7 @@ def _frame_names(frame):
 # reference's preprocessing uses 1 mm on rendered (exact) maps (align_pose.py:49), sensor depth at 1 m is noisy at the millimetre
 INIT_FIT_INLIER_TH = 0.005
 GUARD_KEYS = ("count", "inliers", "rms", "verdict")     # a frame's guard record: (B,P) tensors (pose_utils/pose_fit.py)
+ROT_POOL_KEYS = ("inliers", "count")                    # a frame's record of the consensus rotation read-out: (B,P) int32 tensors
 ST_FIT_KEYS = ("inliers", "valid")                      # a frame's record of the robust scale / translation fit: (B,P) int32 tensors
 
 
@@ -145,6 +146,11 @@ class EvalTrackModel(BaseModel):
         # one for a symmetric category.  The guard, when on, judges the pose this fit produced.  Absent / ransac: False: nothing
         # is launched, no tensor, no pickle entry.
         self.st_fit = self.net.st_fit = self._st_fit_cfg(cfg)
+        # track_cfg: {rot_pool: {consensus: True, angle_th: <degrees>, ...}}: every step's rotation from the consensus of RotationNet's
+        # per-point votes (csrc/rot_consensus.hip, in place of the plain read-out's launch, captured with the step); the scale /
+        # translation fit and the guard consume that rotation unchanged.  Absent / consensus: False: nothing is launched, no tensor,
+        # no pickle entry.
+        self.rot_pool = self.net.rot_pool = self._rot_pool_cfg(cfg)
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
         self.radius = cfg["data_radius"]
         self.det_category = cfg["obj_category"]          # nocs2d_label: the class id the frame's detections are matched against
@@ -227,6 +233,29 @@ class EvalTrackModel(BaseModel):
         if seed < 0:
             raise ValueError(f"track_cfg/st_fit/seed must not be negative, got {seed}")
         return {"inlier_th": frac * float(cfg["data_radius"]), "num_hyps": num_hyps, "seed": seed}
+
+    @staticmethod
+    def _rot_pool_cfg(cfg):
+        """track_cfg/rot_pool, parsed once: None when absent or consensus is not set; angle_th (degrees) has no default -- the right
+        value depends on the trained network's vote scatter --, num_hyps and seed default to init_frame's, as st_fit's do."""
+        s = cfg["track_cfg"].get("rot_pool")
+        if s is None or not s.get("consensus", False):
+            return None
+        angle = s.get("angle_th")
+        if angle is None:
+            raise ValueError("track_cfg/rot_pool/consensus needs track_cfg/rot_pool/angle_th (degrees, inside (0, 180)): it has no default")
+        angle = float(angle)
+        num_hyps = s.get("num_hyps")
+        num_hyps = int(cfg["init_frame"].get("num_hyps", 64) if num_hyps is None else num_hyps)
+        seed = s.get("seed")
+        seed = int(cfg["init_frame"].get("seed", 0) if seed is None else seed)
+        if not 0.0 < angle < 180.0:
+            raise ValueError(f"track_cfg/rot_pool/angle_th must be an angle in degrees inside (0, 180), got {s.get('angle_th')!r}")
+        if not 1 <= num_hyps <= 256:
+            raise ValueError(f"track_cfg/rot_pool/num_hyps must be in [1, 256] (the kernel's limit), got {num_hyps}")
+        if seed < 0:
+            raise ValueError(f"track_cfg/rot_pool/seed must not be negative, got {seed}")
+        return {"angle_th": angle, "num_hyps": num_hyps, "seed": seed}
 
     @staticmethod
     def _yaxis_only(cfg, section, name) -> bool:
@@ -456,6 +485,9 @@ class EvalTrackModel(BaseModel):
             # the robust fit's record joins CoordinateNet's maps (`st_*`), so it travels with them through every batch form
             for k in ST_FIT_KEYS:
                 npcs_pred["st_" + k] = out["st_fit"][k]
+        if self.rot_pool is not None:
+            for k in ROT_POOL_KEYS:                 # (likewise `rot_*`)
+                npcs_pred["rot_" + k] = out["rot_pool"][k]
         return pose if self.guard is None else self._guard_step(input, npcs_pred, pose)
 
     def _guard_step(self, input, npcs_pred, pose):
@@ -764,6 +796,7 @@ class EvalTrackModel(BaseModel):
         pred_poses, npcs_pred = [self._initial_pose()], [None]
         guard = {}                          # frame -> its guard record (guard on)
         st_fit = {}                         # frame -> the robust fit's record (track_cfg/st_fit on)
+        rot_pool = {}                       # frame -> the consensus read-out's record (track_cfg/rot_pool on)
         if self.frame_hook is not None:
             self.frame_hook(0, pred_poses[0])
         self.timer.tick()
@@ -780,6 +813,8 @@ class EvalTrackModel(BaseModel):
                     commit = self._commit_with_record(commit, guard, "guard_", GUARD_KEYS)
                 if self.st_fit is not None:
                     commit = self._commit_with_record(commit, st_fit, "st_", ST_FIT_KEYS)
+                if self.rot_pool is not None:
+                    commit = self._commit_with_record(commit, rot_pool, "rot_", ROT_POOL_KEYS)
                 pending = None                  # (frame, poses that entered it, its deferred checks)
 
                 def settle():
@@ -821,13 +856,15 @@ class EvalTrackModel(BaseModel):
             self.pred_dict["guard"] = [None] + [guard[i] for i in range(1, len(feed))]
         if self.st_fit is not None:
             self.pred_dict["st_fit"] = [None] + [st_fit[i] for i in range(1, len(feed))]
+        if self.rot_pool is not None:
+            self.pred_dict["rot_pool"] = [None] + [rot_pool[i] for i in range(1, len(feed))]
         self.check_l1_stream()
         if save:
             self._save(list(map(_frame_names, feed)))
 
     @staticmethod
     def _commit_with_record(commit, records, prefix, keys):
-        """`commit` of a batch form, with the frame's record (the guard's `guard_*`, the robust fit's `st_*`) taken out of
+        """`commit` of a batch form, with the frame's record (the guard's `guard_*`, the robust fit's `st_*`, the consensus read-out's `rot_*`) taken out of
         CoordinateNet's maps into records[frame]."""
         def wrapped(i, result):
             npcs, pose = commit(i, result)
@@ -868,6 +905,8 @@ class EvalTrackModel(BaseModel):
                 save_dict["guard"][0] = {"yaxis_only": np.ones(len(self.feed_dict[0]["meta"]["path"]), bool)}
         if self.st_fit is not None:
             save_dict["st_fit"] = [None if r is None else {k: v.detach().cpu().numpy() for k, v in r.items()} for r in self.pred_dict["st_fit"]]
+        if self.rot_pool is not None:
+            save_dict["rot_pool"] = [None if r is None else {k: v.detach().cpu().numpy() for k, v in r.items()} for r in self.pred_dict["rot_pool"]]
         records = []
         for i, path in enumerate(self.feed_dict[0]["meta"]["path"]):
             instance, track_num = path.split(".")[-2].split("/")[-3:-1]

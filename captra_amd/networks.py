@@ -222,6 +222,19 @@ class PartCanonNet(nn.Module):
         # the ROBUST scale / translation fit of the tracking step (captra_part_fit_st_ransac): None = the one-pass fit, as ever;
         # {'inlier_th', 'num_hyps', 'seed'} (EvalTrackModel sets it from track_cfg/st_fit) = RANSAC with this net's rotation given
         self.st_fit = None
+        # the ROBUST rotation read-out of the tracking step (captra_rot_pool_consensus): None = the plain mean of the part's votes, as
+        # ever; {'angle_th' (degrees), 'num_hyps', 'seed'} (EvalTrackModel sets it from track_cfg/rot_pool) = the mean of the votes within
+        # angle_th of the best-supported one
+        self.rot_pool = None
+
+    def _robust_rotation(self, input, raw, labels_i32, part_pose):
+        """test_mode with `rot_pool` set: the step's rotation from the heads' raw output (B*P,R,N) by the consensus read-out.
+        input['b0']: the first trajectory's index within the whole batch (the kernel's draws).
+        -> (rotation (B,P,3,3), the frame's record {'inliers', 'count'}: (B,P) int32)."""
+        rp = self.rot_pool
+        rotation, info = fused.rot_pool_consensus(raw, labels_i32, part_pose["rotation"].float().contiguous(), self.sym, rp["angle_th"],
+                                                  num_hyps=rp["num_hyps"], seed=rp["seed"], b0=int(input.get("b0", 0)))
+        return rotation, {"inliers": info["inliers"], "count": info["count"]}
 
     def _robust_fit(self, input, labels_i32, npcs, rotation, part_pose):
         """test_mode with `st_fit` set: the step's scale / translation by the robust fit; an invalid fit keeps the previous values
@@ -237,7 +250,8 @@ class PartCanonNet(nn.Module):
     def forward(self, input, test_mode=False):
         """input: {'points' (B,3,N), 'points_mean' (B,3,1), 'state': {'part': pose}, 'pred_labels',
         'pred_nocs' (B,P,3,N), ...} -> {'part': {'rotation' (B,P,3,3), 'scale' (B,P),
-        'translation' (B,P,3,1)}, 'point_rotation' (B,P,N,3,3)[, 'st_fit': the robust fit's record (test_mode with `st_fit` set)]}."""
+        'translation' (B,P,3,1)}, 'point_rotation' (B,P,N,3,3)[, 'st_fit': the robust fit's record (test_mode with `st_fit` set)]
+        [, 'rot_pool': the consensus read-out's record (test_mode with `rot_pool` set)]}."""
         part_pose = input["state"]["part"]
         P = self.num_parts
         if "canon_pose" in input:
@@ -269,41 +283,56 @@ class PartCanonNet(nn.Module):
             labels_i32 = input.get("pred_labels_i32")
             if labels_i32 is None:
                 labels_i32 = input["pred_labels"].int().contiguous()
-            rotation = fused.rot_pool_compose(raw, labels_i32, part_pose["rotation"].float().contiguous(), self.sym)
+            extra = {}
+            if self.rot_pool is not None:
+                rotation, extra["rot_pool"] = self._robust_rotation(input, raw, labels_i32, part_pose)
+            else:
+                rotation = fused.rot_pool_compose(raw, labels_i32, part_pose["rotation"].float().contiguous(), self.sym)
             npcs = input["pred_nocs"].reshape(B, P, 3, -1).float().contiguous()
             if self.st_fit is not None:
                 pose, record = self._robust_fit(input, labels_i32, npcs, rotation, part_pose)
-                return {"part": pose, "st_fit": record}
+                return {"part": pose, "st_fit": record, **extra}
             # camera points = points + mean and "an invalid fit keeps the previous scale / translation" inside the launch
             scale, trans, _ = part_fit_st_track(labels_i32, npcs, input["points"].float().contiguous(), input["points_mean"], rotation,
                                                 part_pose["scale"], part_pose["translation"], self.sym)
-            return {"part": {"rotation": rotation, "scale": scale, "translation": trans}}
-        seg_rep = cam_seg.unsqueeze(1).expand(-1, P, -1).reshape(B * P, -1)
-        pred = self.regress_net(cam_cn, seg_rep, cam_n3=cam_n3, geom=geom)
+            return {"part": {"rotation": rotation, "scale": scale, "translation": trans}, **extra}
+        extra, robust_rotation = {}, None
+        if eval_rnpcs and test_mode and self.rot_pool is not None:
+            # layer by layer with the consensus read-out: only the diagonal heads' raw output is evaluated (raw_diag) and the kernel
+            # pools it -- there is no torch restatement of the consensus to fall back to
+            if self.return_point_rotation:
+                raise ValueError("track_cfg/rot_pool reads the rotation out of the heads' raw output: return_point_rotation is not available with it")
+            raw = self.regress_net.raw_point_rtvec(cam_cn, cam_n3=cam_n3, geom=geom)           # (B*P,R,N), head p on cloud (b,p)
+            robust_rotation, extra["rot_pool"] = self._robust_rotation(input, raw.float().contiguous(), input["pred_labels"].int().contiguous(),
+                                                                       part_pose)
+            out = {}
+        else:
+            seg_rep = cam_seg.unsqueeze(1).expand(-1, P, -1).reshape(B * P, -1)
+            pred = self.regress_net(cam_cn, seg_rep, cam_n3=cam_n3, geom=geom)
 
-        out = {"rotation": convert_pred_rtvec_to_matrix(pred["rtvec"], self.sym)}       # (B*P,P,3,3)
-        if self.return_point_rotation or not test_mode or self.type == "rot":
-            # per-point rotations are only consumed by the RotationNet experiment's losses (training and its evaluation
-            # pass); skipped while tracking
-            out["point_rotation"] = convert_pred_rtvec_to_matrix(pred["point_rtvec"].transpose(-1, -2), self.sym)
-        diag = torch.arange(P, device=out["rotation"].device)
-        for key in list(out.keys()):                                                     # head p on cloud p
-            raw = out[key].reshape((B, P) + out[key].shape[1:])
-            out[key] = raw[:, diag, diag]
+            out = {"rotation": convert_pred_rtvec_to_matrix(pred["rtvec"], self.sym)}       # (B*P,P,3,3)
+            if self.return_point_rotation or not test_mode or self.type == "rot":
+                # per-point rotations are only consumed by the RotationNet experiment's losses (training and its evaluation
+                # pass); skipped while tracking
+                out["point_rotation"] = convert_pred_rtvec_to_matrix(pred["point_rtvec"].transpose(-1, -2), self.sym)
+            diag = torch.arange(P, device=out["rotation"].device)
+            for key in list(out.keys()):                                                     # head p on cloud p
+                raw = out[key].reshape((B, P) + out[key].shape[1:])
+                out[key] = raw[:, diag, diag]
 
         if self.type == "rot":
             final_pose = merge_reenact_canon_part_pose(part_pose, out)
             for key in ("translation", "scale"):
                 final_pose[key] = input["gt_part"][key].detach().clone()
         elif eval_rnpcs:
-            rotation = merge_reenact_canon_part_pose(part_pose, out)["rotation"]
+            rotation = merge_reenact_canon_part_pose(part_pose, out)["rotation"] if robust_rotation is None else robust_rotation
             labels = input["pred_labels"] if test_mode else input["labels"]
             fit_rot = rotation if test_mode else input["gt_part"]["rotation"]
             npcs = input["pred_nocs"].reshape(B, P, 3, -1).float().contiguous()
             if test_mode and self.st_fit is not None:
                 # (no `where` below: the kernel keeps the previous values of an invalid fit)
                 final_pose, record = self._robust_fit(input, labels.int().contiguous(), npcs, rotation.float().contiguous(), part_pose)
-                ret = {"part": final_pose, "st_fit": record}
+                ret = {"part": final_pose, "st_fit": record, **extra}
                 if "point_rotation" in out:
                     ret["point_rotation"] = out["point_rotation"]
                 return ret
@@ -319,7 +348,7 @@ class PartCanonNet(nn.Module):
         else:
             raise ValueError(f"unsupported network type {self.type}")
 
-        ret = {"part": final_pose}
+        ret = {"part": final_pose, **extra}
         if "point_rotation" in out:
             ret["point_rotation"] = out["point_rotation"]
         return ret

@@ -32,6 +32,10 @@ _FLAGS = [  # (name, type, default)
     # the robust scale / translation fit of every step (model.py: EvalTrackModel.st_fit); off unless ransac is True
     ("track_cfg/st_fit/ransac", boolean_string, None), ("track_cfg/st_fit/inlier_th", float, None), ("track_cfg/st_fit/num_hyps", int, None),
     ("track_cfg/st_fit/seed", int, None),
+    # the consensus rotation read-out of every step (model.py: EvalTrackModel.rot_pool); off unless consensus is True, and then angle_th
+    # (degrees) is required
+    ("track_cfg/rot_pool/consensus", boolean_string, None), ("track_cfg/rot_pool/angle_th", float, None),
+    ("track_cfg/rot_pool/num_hyps", int, None), ("track_cfg/rot_pool/seed", int, None),
     # optimisation
     ("total_epoch", int, None), ("optimizer", str, None), ("weight_decay", float, None), ("learning_rate", float, None),
     ("lr_policy", str, None), ("lr_gamma", float, None), ("lr_step_size", int, None), ("lr_clip", float, None), ("freq/save", int, None),

@@ -785,6 +785,36 @@ int captra_pack_pose(int n, const float *rot, const float *trans, const float *s
 int captra_rot_pool_compose(int b, int p, int n, int sym, int diag_only, const float *raw, const int *labels,
                             const float *prev_rot, float *rot, float *delta, captra_stream_t stream);
 
+/* Robust rotation read-out: captra_rot_pool_compose with a consensus over the per-point votes in place of the plain mean of all of
+ * them -- a minority of votes that agree with each other (a second surface inside a detector's mask) drags a mean, which has no
+ * breakdown point.  A vote is a complete rotation hypothesis already (minimal sample size 1), so this is a RANSAC without a solver.
+ * One launch, one workgroup per (b, p).  P outside [1, 8], num_hyps outside [1, 256], N outside [1, 16384], sym or diag_only outside
+ * {0, 1}, b0 < 0 or b0 > INT_MAX - b, cos_th not strictly inside (-1, 1) (a NaN included) return -1 without a launch; b = 0 returns 0.
+ *   raw, labels, prev_rot, diag_only, rot, delta: exactly as for captra_rot_pool_compose.
+ *   vote i  :  the per-point prediction of point i, computed as captra_rot_pool_compose computes it (the same fp32 operations in
+ *              the same order): sym = 1 the unit axis normalize3(raw[0..3)); sym = 0 the ortho6d frame with columns x, y, z.
+ *   members :  the points with label p, in ascending point index; count of them.
+ *   hypothesis h: the vote of member rank r_h.  sample_rank (B,P,H) i32 given: r_h = sample_rank[b][p][h] mod count (as unsigned);
+ *              NULL: r_h = u(0) mod count with u the draw generator of captra_part_fit_ransac, b0 + b in place of b in the key and
+ *              draw index 0, so that a lane of a batch draws what the whole batch draws.  Duplicates are allowed; with count = 0
+ *              nothing is drawn.
+ *   score(h):  the number of member votes i that are inliers of h; every operation a separately rounded fp32 one, a dot product
+ *              (a0 b0 + a1 b1) + a2 b2.  sym = 1: d = v_h . v_i, inlier iff d > cos_th.  sym = 0: tr = ((x_h.x_i) + (y_h.y_i)) +
+ *              (z_h.z_i) -- the trace of V_h^T V_i = 1 + 2 cos(angle between the two frames) --, inlier iff tr > 1.f + 2.f * cos_th.
+ *              A NaN compares false.  best = the FIRST h with the largest score.
+ *   result  :  the masked mean of the votes that are inliers of best, followed by exactly the tail of captra_rot_pool_compose:
+ *              (0,1,0) / identity when there is nothing to average, the frame from the y-axis / Gram-Schmidt, prev_rot * dR in fp32.
+ *              The pooling loop, its reduction and the tail are the plain read-out's own code under the predicate member && inlier
+ *              (csrc/rot_pool.h): when every member is an inlier of best, rot and delta are captra_rot_pool_compose's bits.
+ *   -> rot (B,P,3,3), delta (B,P,3,3) or NULL; optional (NULL = not wanted) count, num_inliers, best (B,P) i32.  count = 0:
+ *      num_inliers = best = 0 and dR is the default.  num_inliers = 0 with members happens when no vote is an inlier even of itself
+ *      (a vote with a NaN, or a degenerate frame): dR is the default then too.  Points that are not members may hold NaN / Inf; they
+ *      reach no output, and no NaN leaves the kernel when prev_rot is finite.
+ * Outputs must not alias inputs. */
+int captra_rot_pool_consensus(int b, int p, int n, int sym, int diag_only, int b0, int num_hyps, float cos_th, const float *raw,
+                              const int *labels, const float *prev_rot, const int *sample_rank, unsigned long long seed, float *rot,
+                              float *delta, int *count, int *num_inliers, int *best, captra_stream_t stream);
+
 /* Batched 3x3 orthogonal Procrustes: R = U diag(1,1,det(U V^T)) V^T with U S V^T = tgt^T src
  * (rotate_pts_batch procrustes.py:25-56).  src, tgt (nb,N,3) -> rot (nb,3,3).  One-sided Jacobi. */
 int captra_procrustes_rot3(int nb, int n, const float *src, const float *tgt, float *rot,
