@@ -581,15 +581,7 @@ def test_group_points_grad_csr_path_vs_float64(pn, device, c, n, m, k):
     assert float((np.abs(grad_atomic.cpu().numpy() - ref64) / scale).max()) <= 8e-6
 
 
-def clouds_ball_idx(rng, n, m, k):
-    """Index lists shaped like a ball query's: a few distinct neighbours per centre, padded with the first."""
-    idx = np.empty((m, k), np.int32)
-    for j in range(m):
-        cnt = int(rng.integers(1, k + 1))
-        hits = np.sort(rng.choice(n, size=min(cnt, n), replace=False)).astype(np.int32)
-        idx[j, :len(hits)] = hits
-        idx[j, len(hits):] = hits[0]
-    return idx
+from tests.scatter_judge import ball_like as clouds_ball_idx  # noqa: E402  (lists shaped like a ball query's; they live with the judge of these kernels)
 
 
 @pytest.mark.parametrize("c,m,n", [(128, 512, 4096), (256, 128, 512), (9, 50, 333)])
