@@ -134,6 +134,7 @@ _AUX_SIGNATURES = {
     "captra_chain_bf16_image_bytes": ([_INT, _INT], _LL),
     "captra_dense_x6_image_bytes": ([_INT, _INT], _LL),
     "captra_sa_x6_image_bytes": ([_INT] * 4, _LL),
+    "captra_chain_x6_image_bytes": ([_INT, _P, _P], _LL),
     "captra_sa_bf16_image_bytes": ([_INT] * 4, _LL),
     "captra_sa1_stream_scratch_bytes": ([_INT, _INT], _LL),
     "captra_sa1_stream_set_grid": ([_INT, _INT], None),

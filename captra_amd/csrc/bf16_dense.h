@@ -1,29 +1,9 @@
-// Shared device helpers of the bf16-native dense kernels (csrc/dense_bf16.hip, csrc/tile_bf16.hip): packing, the MFMA wrapper,
-// the slot-order permutation, the statistics butterfly and the on-load GroupNorm transform.
+// Shared device helpers of the bf16-native dense kernels (csrc/dense_bf16.hip, csrc/tile_bf16.hip, csrc/neck_bf16.hip): the statistics
+// butterfly and the on-load GroupNorm transform, on the pair primitives of csrc/mfma_bf16.h.
 #pragma once
-#include "common.h"
+#include "mfma_bf16.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned db_pack(float lo, float hi) {
-    const f32x2 f = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-__device__ __forceinline__ unsigned db_relu2(unsigned v) {
-    const s16x2 z = {0, 0};
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), z));
-}
-__device__ __forceinline__ f32x16 db_mfma(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__host__ __device__ __forceinline__ int db_perm(int s) { return (s & 3) | ((s & 4) << 1) | ((s & 8) >> 1); }
 
 // ST epilogue: per-channel (sum, sum of squares) of what a wave just stored for one row tile -- 16 channels x (TN x 32)
 // positions per half-wave -- reduced over the 32 columns by a halving butterfly (16 + 8 + 4 + 2 + 1 exchanges instead of
@@ -54,7 +34,7 @@ __device__ __forceinline__ void db_stats_tile(float (&vals)[32], int col, int h,
 __device__ __forceinline__ void db_stats_acc(float (&vals)[32], int jj, u32x4 v) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float lo = __uint_as_float(v[i] << 16), hi = __uint_as_float(v[i] & 0xffff0000u);
+        const float lo = bf_lo(v[i]), hi = bf_hi(v[i]);
         vals[8 * jj + 2 * i] += lo;
         vals[8 * jj + 2 * i + 1] += hi;
         vals[16 + 8 * jj + 2 * i] = __builtin_fmaf(lo, lo, vals[16 + 8 * jj + 2 * i]);
@@ -71,8 +51,8 @@ __device__ __forceinline__ u32x4 db_affine(u32x4 v, const float *t) {
     u32x4 r;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float lo = __uint_as_float(v[i] << 16), hi = __uint_as_float(v[i] & 0xffff0000u);
-        r[i] = db_relu2(db_pack(__builtin_fmaf(lo, a[2 * i], b[2 * i]), __builtin_fmaf(hi, a[2 * i + 1], b[2 * i + 1])));
+        const float lo = bf_lo(v[i]), hi = bf_hi(v[i]);
+        r[i] = bf_relu2(bf_pack(__builtin_fmaf(lo, a[2 * i], b[2 * i]), __builtin_fmaf(hi, a[2 * i + 1], b[2 * i + 1])));
     }
     return r;
 }

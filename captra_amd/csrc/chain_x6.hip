@@ -1,4 +1,4 @@
-// f32x6 dense layer CHAINS for gfx950 (arithmetic contract: include/captra_hip.h "f32x6", csrc/sa_x6.hip): the 4096-point tails of
+// f32x6 dense layer CHAINS for gfx950 (arithmetic contract and shared primitives: csrc/x6.h): the 4096-point tails of
 // the backbone in the opt-in arithmetic --
 //   captra_mlp_chain3_x6:  y = act3(W3 relu(W2 relu(W1 x + b1) + b2) + b3), the FP1 shared MLP + the backbone's conv1
 //                          (reference network/models/pointnet_utils.py:296-298, backbones.py:66-68; exact form: csrc/mlp_chain.hip);
@@ -13,52 +13,9 @@
 // channels: nine k-steps; its operand is the position's input column, loaded and split at the head of a slice), and the last
 // layer STORES (128-byte row segments per half-wave) instead of reducing.
 #include "common.h"
-#include <type_traits>
+#include "x6.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int cx_i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int cx_cdiv(int a, int b) { return (a + b - 1) / b; }
-constexpr int cx_pad4(int a) { return (a + 3) / 4 * 4; }
-
-__device__ __forceinline__ unsigned cx_pack(float lo, float hi) {          // one v_cvt_pk_bf16_f32 (RNE)
-    const f32x2 f = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-__device__ __forceinline__ float cx_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float cx_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ void cx_split2(float a, float b, unsigned &p0, unsigned &p1, unsigned &p2) {
-    p0 = cx_pack(a, b);
-    const float ra = a - cx_lo(p0), rb = b - cx_hi(p0);
-    p1 = cx_pack(ra, rb);
-    p2 = cx_pack(ra - cx_lo(p1), rb - cx_hi(p1));
-    asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2));        // pinned where it is written (sa_x6.hip: LLVM sinks the split to its first use)
-}
-__device__ __forceinline__ f32x16 cx_mfma(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// the six products of one k-step as two accumulator chains issued alternately (sa_x6.hip: sx_group)
-__device__ __forceinline__ void cx_group(f32x16 &hi, f32x16 &lo, const u32x4 (&w)[3], const u32x4 &x0, const u32x4 &x1, const u32x4 &x2) {
-    lo = cx_mfma(w[2], x0, lo); hi = cx_mfma(w[1], x0, hi); lo = cx_mfma(w[0], x2, lo);
-    hi = cx_mfma(w[0], x1, hi); lo = cx_mfma(w[1], x1, lo); hi = cx_mfma(w[0], x0, hi);
-}
-template <int I, int N, typename F>
-__device__ __forceinline__ void cx_static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        cx_static_for<I + 1, N>(f);
-    }
-}
-__host__ __device__ constexpr int cx_perm(int s) { return (s & 3) | ((s & 4) << 1) | ((s & 8) >> 1); }
-constexpr int cx_unit_group(int u, int kst) { return kst > 1 ? 1 + u * (kst - 1) / 8 : 0; }
-
-#define CX_WAIT_VM(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | (((N) >> 4) << 14) | 0x0F70)
 
 // The layer table.  TAIL = false: three layers C0 -> 128 -> 128 -> 128 (the last stored).  TAIL = true: six -- C0 -> 128 -> 128 -> 128
 // (feat), feat -> SEG (stored), feat -> 128 -> NOCS (stored).  Activations live in two register buffers: A (nine k-steps: the input
@@ -67,10 +24,10 @@ template <int C0, bool TAIL>
 struct CxShape {
     static constexpr int C = 128;
     static constexpr int NL = TAIL ? 6 : 3;
-    static constexpr int KST0 = cx_cdiv(C0, 16);
+    static constexpr int KST0 = x6_cdiv(C0, 16);
     static constexpr int kst(int l) { return l == 0 ? KST0 : 8; }
     static constexpr int nt(int l) { return (TAIL && (l == 3 || l == 5)) ? 1 : 4; }
-    static constexpr int frags(int l) { return cx_pad4(kst(l) * 3); }          // one chunk = one row tile of a layer
+    static constexpr int frags(int l) { return x6_pad4(kst(l) * 3); }          // one chunk = one row tile of a layer
     static constexpr bool in_a(int l) { return l == 0 || l == 2 || l == 5; }    // the layer's operand buffer
     static constexpr bool out_a(int l) { return l == 1 || l == 4; }             // where a hidden layer's output goes
     static constexpr bool stores(int l) { return TAIL ? (l == 3 || l == 5) : l == 2; }
@@ -91,26 +48,14 @@ struct CxShape {
 };
 
 // ---- image builder: one layer per launch --------------------------------------------------------------------------------------
-// wt: the layer's packed fp32 W'^T (row-major part, element [k * ldw + cout]).  Fragment (tile t, k-step kk, part): lane l = row
-// 32 t + (l & 31), k-slots 8 (l >> 5) .. + 7; slot s holds channel 16 kk + s (natural: the first layer, whose operand is loaded in
-// that order) or 16 kk + perm(s) (the in-register hand-over order).
+// wt: the layer's packed fp32 W'^T (row-major part, element [k * ldw + cout]).  The layer's fragment block (x6.h x6_frag_bits:
+// natural k order for the first layer, whose operand is loaded in that order, the hand-over order for the others), then its biases.
 __global__ void pack_chain_x6_kernel(int cin, int cout, int ldw, int natural, const float *__restrict__ wt, const float *__restrict__ bias,
                                      unsigned char *__restrict__ img, float *__restrict__ bias_out) {
-    const int kst = (cin + 15) / 16, nt = (cout + 31) / 32, ch = (kst * 3 + 3) / 4 * 4;
+    const int nt = x6_cdiv(cout, 32), ch = x6_pad4(x6_cdiv(cin, 16) * 3);
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < (long long)nt * ch * 512) {
-        const int f = (int)(e >> 9), lane = (int)(e >> 3) & 63, el = (int)e & 7;
-        const int slot = 8 * (lane >> 5) + el;
-        const int t = f / ch, r = f % ch, kk = r / 3, part = r % 3;
-        const int row = 32 * t + (lane & 31), k = 16 * kk + (natural ? slot : cx_perm(slot));
-        float v = 0.f;
-        if (kk < kst && row < cout && k < cin) v = wt[(size_t)k * ldw + row];
-        const __bf16 h0 = (__bf16)v;
-        const float r1 = v - (float)h0;
-        const __bf16 h1 = (__bf16)r1;
-        const __bf16 h2 = (__bf16)(r1 - (float)h1);
-        const __bf16 hh = part == 0 ? h0 : (part == 1 ? h1 : h2);
-        reinterpret_cast<unsigned short *>(img)[e] = __builtin_bit_cast(unsigned short, hh);
+        reinterpret_cast<unsigned short *>(img)[e] = x6_frag_bits(e, cin, cout, ldw, natural != 0, wt);
     } else {
         const int i = (int)(e - (long long)nt * ch * 512);
         if (i < 128) bias_out[i] = i < cout ? bias[i] : 0.f;
@@ -139,26 +84,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int h = lane >> 5, col = lane & 31;
 
     const unsigned long long img_addr = reinterpret_cast<unsigned long long>(p.img);
-    const cx_i32x4 wsrc = {(int)(unsigned)img_addr, (int)(unsigned)(img_addr >> 32), S::WBYTES, 0x00020000};
+    const x6_i32x4 wsrc = {(int)(unsigned)img_addr, (int)(unsigned)(img_addr >> 32), S::WBYTES, 0x00020000};
     const unsigned lds0 = (unsigned)reinterpret_cast<size_t>((__attribute__((address_space(3))) unsigned char *)smem);
     const unsigned voff16 = lane * 16;
     // (chunk / group numbers travel as integral constants: the layer table's constexpr walks must fold at compile time -- called on a
     // lambda's run-time parameter they become real loops, 4600 branches and 134 KB of code in the six-layer kernel)
-    auto issue_chunk = [&](auto c_c) __attribute__((always_inline)) {          // (asm, buffer form: see sa_x6.hip)
+    auto issue_chunk = [&](auto c_c) __attribute__((always_inline)) {
         constexpr int c = decltype(c_c)::value;
-        constexpr int slot_off = (c % NS) * S::SLOTB, img_off = S::chunk_off(c), pieces = S::frags(S::layer_of(c)) / 4;
-        const unsigned dst = lds0 + slot_off + wave * 1024;
-        const unsigned soff = img_off + wave * 1024;
-        const unsigned vo = voff16;                         // (copies: an asm operand alone does not capture in a generic lambda)
-        const cx_i32x4 ws = wsrc;
-#pragma unroll
-        for (int i = 0; i < pieces; ++i)
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                         :: "s"(dst + i * 4096), "v"(vo), "s"(ws), "s"(soff + i * 4096) : "memory");
+        constexpr int slot_off = (c % NS) * S::SLOTB, img_off = S::chunk_off(c), frags = S::frags(S::layer_of(c));
+        x6_ring_issue(lds0 + slot_off, voff16, wsrc, img_off, wave, frags);
     };
     auto acquire = [&](auto c_c) __attribute__((always_inline)) {
         constexpr int c = decltype(c_c)::value;
-        CX_WAIT_VM(0);
+        X6_WAIT_VM(0);
         __builtin_amdgcn_s_barrier();
         issue_chunk(std::integral_constant<int, (c + 1) % S::NCH>{});
     };
@@ -166,7 +104,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     issue_chunk(std::integral_constant<int, 0>{});
     for (int e = tid; e < S::NBIAS / 4; e += 256)
         reinterpret_cast<uint4 *>(bias_lds)[e] = reinterpret_cast<const uint4 *>(p.img + S::WBYTES)[e];
-    CX_WAIT_VM(0);
+    X6_WAIT_VM(0);
     __syncthreads();
     issue_chunk(std::integral_constant<int, 1>{});
 
@@ -220,7 +158,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 unsigned p0, p1, p2;
-                cx_split2(raw[kk][2 * i], raw[kk][2 * i + 1], p0, p1, p2);
+                x6_split2_pinned(raw[kk][2 * i], raw[kk][2 * i + 1], p0, p1, p2);
                 ha[0][kk][i] = p0; ha[1][kk][i] = p1; ha[2][kk][i] = p2;
             }
         __builtin_amdgcn_sched_barrier(0);
@@ -244,14 +182,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             } else {
                 const float a = relu_bits(acc[8 * jj + 2 * i]), b2 = relu_bits(acc[8 * jj + 2 * i + 1]);
                 unsigned p0, p1, p2;
-                cx_split2(a, b2, p0, p1, p2);
+                x6_split2_pinned(a, b2, p0, p1, p2);
                 if constexpr (S::out_a(l)) { ha[0][2 * t + jj][i] = p0; ha[1][2 * t + jj][i] = p1; ha[2][2 * t + jj][i] = p2; }
                 else { hb[0][2 * t + jj][i] = p0; hb[1][2 * t + jj][i] = p1; hb[2][2 * t + jj][i] = p2; }
             }
         };
 
         f32x16 acc[2], accl[2];
-        cx_static_for<0, S::G>([&](auto gi_c) __attribute__((always_inline)) {
+        x6_static_for<0, S::G>([&](auto gi_c) __attribute__((always_inline)) {
             constexpr int gi = decltype(gi_c)::value;
             constexpr int tau = S::tile_of_group(gi);
             constexpr int kk = gi - S::group0(tau);
@@ -272,17 +210,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             if constexpr (tau > 0) {
                 constexpr int lp = S::layer_of(tau - 1), tp = tau - 1 - S::tile0(lp);
                 if constexpr (kk == (kst > 1 ? 1 : 0)) acc[(tau - 1) & 1] += accl[(tau - 1) & 1];
-                cx_static_for<0, 8>([&](auto u_c) __attribute__((always_inline)) {
-                    if constexpr (cx_unit_group(decltype(u_c)::value, kst) == kk)
+                x6_static_for<0, 8>([&](auto u_c) __attribute__((always_inline)) {
+                    if constexpr (x6_unit_group(decltype(u_c)::value, kst) == kk)
                         readout(std::integral_constant<int, lp>{}, std::integral_constant<int, tp>{}, u_c, acc[(tau - 1) & 1]);
                 });
             }
             // ---- the six products ----
-            if constexpr (S::in_a(l)) cx_group(acc[tau & 1], accl[tau & 1], wr[gi & 1], ha[0][kk], ha[1][kk], ha[2][kk]);
-            else cx_group(acc[tau & 1], accl[tau & 1], wr[gi & 1], hb[0][kk], hb[1][kk], hb[2][kk]);
+            if constexpr (S::in_a(l)) x6_group<false>(acc[tau & 1], accl[tau & 1], wr[gi & 1], ha[0][kk], ha[1][kk], ha[2][kk]);
+            else x6_group<false>(acc[tau & 1], accl[tau & 1], wr[gi & 1], hb[0][kk], hb[1][kk], hb[2][kk]);
             {
-                constexpr int nu = (tau > 0) ? ((cx_unit_group(0, kst) == kk) + (cx_unit_group(1, kst) == kk) + (cx_unit_group(2, kst) == kk) + (cx_unit_group(3, kst) == kk) +
-                                                 (cx_unit_group(4, kst) == kk) + (cx_unit_group(5, kst) == kk) + (cx_unit_group(6, kst) == kk) + (cx_unit_group(7, kst) == kk)) : 0;
+                constexpr int nu = (tau > 0) ? ((x6_unit_group(0, kst) == kk) + (x6_unit_group(1, kst) == kk) + (x6_unit_group(2, kst) == kk) + (x6_unit_group(3, kst) == kk) +
+                                                 (x6_unit_group(4, kst) == kk) + (x6_unit_group(5, kst) == kk) + (x6_unit_group(6, kst) == kk) + (x6_unit_group(7, kst) == kk)) : 0;
                 constexpr int per = (nu * 13 + 5) / 6;
                 if constexpr (per > 0) {
 #pragma unroll
@@ -298,7 +236,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         {
             constexpr int TL = S::NCH - 1, lp = S::layer_of(TL), tp = TL - S::tile0(lp);
             acc[TL & 1] += accl[TL & 1];
-            cx_static_for<0, 8>([&](auto u_c) __attribute__((always_inline)) {
+            x6_static_for<0, 8>([&](auto u_c) __attribute__((always_inline)) {
                 readout(std::integral_constant<int, lp>{}, std::integral_constant<int, tp>{}, u_c, acc[TL & 1]);
             });
         }
@@ -306,7 +244,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // spilled the six-layer kernel: the column is fetched here, at the slice's edge)
         if (has_next) load_raw(jobn, raw);
     }
-    CX_WAIT_VM(0);                                        // nothing of the ring may land in LDS after the workgroup is gone
+    X6_WAIT_VM(0);                                        // nothing of the ring may land in LDS after the workgroup is gone
 }
 
 template <int C0, int SEG, int NOCS, bool TAIL>
@@ -328,7 +266,7 @@ int cx_launch(const CxParams &p, hipStream_t stream) {
 extern "C" long long captra_chain_x6_image_bytes(int nl, const int *cin, const int *cout) {
     if (nl < 1 || nl > 6) return -1;
     long long frags = 0;
-    for (int l = 0; l < nl; ++l) frags += (long long)((cout[l] + 31) / 32) * ((((cin[l] + 15) / 16) * 3 + 3) / 4 * 4);
+    for (int l = 0; l < nl; ++l) frags += (long long)x6_cdiv(cout[l], 32) * x6_pad4(x6_cdiv(cin[l], 16) * 3);
     return frags * 1024 + (long long)nl * 128 * 4;
 }
 
@@ -338,7 +276,7 @@ extern "C" long long captra_chain_x6_image_bytes(int nl, const int *cin, const i
 extern "C" int captra_pack_chain_x6(int l, int cin, int cout, int natural, long long frag_off, long long total_frag_bytes, const float *wt,
                                     const float *bias, unsigned char *img, captra_stream_t stream) {
     if (l < 0 || l > 5 || cin < 1 || cout < 1 || cout > 128 || wt == nullptr || bias == nullptr || img == nullptr) return -1;
-    const int kst = (cin + 15) / 16, nt = (cout + 31) / 32, ch = (kst * 3 + 3) / 4 * 4;
+    const int nt = x6_cdiv(cout, 32), ch = x6_pad4(x6_cdiv(cin, 16) * 3);
     const long long threads = (long long)nt * ch * 512 + 128;
     CAPTRA_LAUNCH("pack_weights", pack_chain_x6_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cin, cout,
                   (cout + 127) / 128 * 128, natural, wt, bias, img + frag_off, reinterpret_cast<float *>(img + total_frag_bytes) + 128 * l);

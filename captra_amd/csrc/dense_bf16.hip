@@ -27,7 +27,7 @@ __global__ void pack_dense_bf16_kernel(int cin, int cout, int ldw, int perm, con
     const int f = e >> 9, lane = (e >> 3) & 63, el = e & 7;
     const int t = f / kst, kk = f % kst;
     const int slot = 8 * (lane >> 5) + el;
-    const int row = 32 * t + (lane & 31), k = 16 * kk + (perm ? db_perm(slot) : slot);
+    const int row = 32 * t + (lane & 31), k = 16 * kk + (perm ? bf_perm(slot) : slot);
     const float v = (row < cout && k < cin) ? wt[(size_t)k * ldw + row] : 0.f;
     const __bf16 h = (__bf16)v;
     img[e] = __builtin_bit_cast(unsigned short, h);
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256, 2) void pw_bf16pm_kernel(DbParams p) {
         const float *abp = p.ab + (size_t)b * p.cin * 2;
         for (int e = tid; e < p.kst * 32; e += 256) {
             const int kk = e >> 5, hh = (e >> 4) & 1, i = e & 15;
-            const int c = 16 * kk + db_perm(8 * hh + (i & 7));
+            const int c = 16 * kk + bf_perm(8 * hh + (i & 7));
             aff_tab[e] = c < p.cin ? abp[2 * c + (i >> 3)] : 0.f;
         }
         __syncthreads();
@@ -138,10 +138,10 @@ __global__ __launch_bounds__(256, 2) void pw_bf16pm_kernel(DbParams p) {
                 if constexpr (AFF) bb = db_affine(bb, aff_tab + (kk * 2 + h) * 16);
             } else {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) bb[i] = db_pack(Bf[s][tn][2 * i], Bf[s][tn][2 * i + 1]);
+                for (int i = 0; i < 4; ++i) bb[i] = bf_pack(Bf[s][tn][2 * i], Bf[s][tn][2 * i + 1]);
             }
 #pragma unroll
-            for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = db_mfma(A[s][tm], bb, acc[tm][tn]);
+            for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = bf_mfma(A[s][tm], bb, acc[tm][tn]);
         }
     };
     load(0, 0);
@@ -180,8 +180,8 @@ __global__ __launch_bounds__(256, 2) void pw_bf16pm_kernel(DbParams p) {
                     u32x4 v;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        v[i] = db_pack(acc[tm][tn][8 * jj + 2 * i], acc[tm][tn][8 * jj + 2 * i + 1]);
-                        if (p.act == ACT_RELU) v[i] = db_relu2(v[i]);
+                        v[i] = bf_pack(acc[tm][tn][8 * jj + 2 * i], acc[tm][tn][8 * jj + 2 * i + 1]);
+                        if (p.act == ACT_RELU) v[i] = bf_relu2(v[i]);
                     }
                     *reinterpret_cast<u32x4 *>(yp + 16 * jj) = v;
                     if constexpr (ST) db_stats_acc(sv, jj, v);
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256, 2) void pw_bf16pm_affs_kernel(DbParams p) {
         const float *abp = p.ab + (size_t)b * p.cin * 2;
         for (int e = tid; e < kst * 32; e += 256) {
             const int kk = e >> 5, hh = (e >> 4) & 1, i = e & 15;
-            const int c = 16 * kk + db_perm(8 * hh + (i & 7));
+            const int c = 16 * kk + bf_perm(8 * hh + (i & 7));
             aff_tab[e] = c < p.cin ? abp[2 * c + (i >> 3)] : 0.f;
         }
     }
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256, 2) void pw_bf16pm_affs_kernel(DbParams p) {
                 for (int tn = 0; tn < TN; ++tn) {
                     const u32x4 bb = *reinterpret_cast<const u32x4 *>(src + (ks * TN + tn) * 1024 + lane * 16);
 #pragma unroll
-                    for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = db_mfma(A[ks % NS][tm], bb, acc[tm][tn]);
+                    for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = bf_mfma(A[ks % NS][tm], bb, acc[tm][tn]);
                 }
             }
             if (ks == 1) {
@@ -330,8 +330,8 @@ __global__ __launch_bounds__(256, 2) void pw_bf16pm_affs_kernel(DbParams p) {
                     u32x4 v;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        v[i] = db_pack(acc[tm][tn][8 * jj + 2 * i], acc[tm][tn][8 * jj + 2 * i + 1]);
-                        if (p.act == ACT_RELU) v[i] = db_relu2(v[i]);
+                        v[i] = bf_pack(acc[tm][tn][8 * jj + 2 * i], acc[tm][tn][8 * jj + 2 * i + 1]);
+                        if (p.act == ACT_RELU) v[i] = bf_relu2(v[i]);
                     }
                     *reinterpret_cast<u32x4 *>(yp + 16 * jj) = v;
                     if constexpr (ST) db_stats_acc(sv, jj, v);
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(256) void gn_stats_bf16pm_kernel(int c, int cp, lon
         const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float lo = __uint_as_float(w[i] << 16), hi = __uint_as_float(w[i] & 0xffff0000u);
+            const float lo = bf_lo(w[i]), hi = bf_hi(w[i]);
             s[2 * i] += lo; q[2 * i] = __builtin_fmaf(lo, lo, q[2 * i]);
             s[2 * i + 1] += hi; q[2 * i + 1] = __builtin_fmaf(hi, hi, q[2 * i + 1]);
         }
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256) void gn_stats_bf16pm_kernel(int c, int cp, lon
             sm += red[(k * G + g2) * 16 + e];
             sq += red[(k * G + g2) * 16 + 8 + e];
         }
-        const int ch = 16 * (g2 >> 1) + db_perm(8 * (g2 & 1) + e);
+        const int ch = 16 * (g2 >> 1) + bf_perm(8 * (g2 & 1) + e);
         if (ch < c) {
             float *dst = stats + (((size_t)b * c + ch) * T + chunk) * 2;
             dst[0] = sm;

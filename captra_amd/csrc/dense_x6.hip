@@ -1,5 +1,5 @@
 // f32x6 dense layer for gfx950: y = act(W x' + b) over (B, cin, L) -> (B, cout, L) with every product on
-// v_mfma_f32_32x32x16_bf16 as six bf16 products of three-way splits (arithmetic contract: include/captra_hip.h "f32x6", csrc/sa_x6.hip),
+// v_mfma_f32_32x32x16_bf16 as six bf16 products of three-way splits (arithmetic contract and shared primitives: csrc/x6.h),
 // for the Conv1d -> GroupNorm -> ReLU chains of the rotation heads (reference network/models/blocks.py:150-165, 168-193):
 // x' = relu(a x + b) with the previous layer's per-(cloud, channel) GroupNorm coefficients applied while the operand is staged,
 // (sum, sum of squares) of the raw output per channel and 128 positions from the epilogue -- the interface of
@@ -21,32 +21,9 @@
 // The MFMAs are FLIPPED (positions = rows): a lane owns a channel, so the statistics are sums over its own registers; the output
 // tile leaves through LDS as whole 512-byte rows.
 #include "common.h"
-#include <type_traits>
+#include "x6.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int dx_i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned dx_pack(float lo, float hi) {
-    const f32x2 f = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-__device__ __forceinline__ float dx_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float dx_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ void dx_split2(float a, float b, unsigned &p0, unsigned &p1, unsigned &p2) {
-    p0 = dx_pack(a, b);
-    const float ra = a - dx_lo(p0), rb = b - dx_hi(p0);
-    p1 = dx_pack(ra, rb);
-    p2 = dx_pack(ra - dx_lo(p1), rb - dx_hi(p1));
-}
-__device__ __forceinline__ f32x16 dx_mfma(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 constexpr int DX_TP = 128, DX_TC = 256;                // positions / channels per workgroup
 constexpr int DX_ASTAGE = 24 * 1024, DX_BSTAGE = 12 * 1024, DX_STAGE = DX_ASTAGE + DX_BSTAGE;
@@ -63,12 +40,7 @@ __global__ void pack_dense_x6_kernel(int cin, int cout, int ldw, const float *__
     const int part = (int)(f % 3), t = (int)((f / 3) % 8), kk = (int)((f / 24) % kst), cb = (int)(f / (24ll * kst));
     const int ch = DX_TC * cb + 32 * t + (lane & 31), k = 16 * kk + 8 * (lane >> 5) + el;
     const float v = (ch < cout && k < cin) ? wt[(size_t)k * ldw + ch] : 0.f;
-    const __bf16 h0 = (__bf16)v;
-    const float r1 = v - (float)h0;
-    const __bf16 h1 = (__bf16)r1;
-    const __bf16 h2 = (__bf16)(r1 - (float)h1);
-    const __bf16 h = part == 0 ? h0 : (part == 1 ? h1 : h2);
-    reinterpret_cast<unsigned short *>(img)[e] = __builtin_bit_cast(unsigned short, h);
+    reinterpret_cast<unsigned short *>(img)[e] = x6_part_bits(v, part);
 }
 
 struct DxParams {
@@ -91,7 +63,6 @@ struct DxParams {
 #else
 #define DX_ABL 0
 #endif
-#define DX_WAIT_VM(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | (((N) >> 4) << 14) | 0x0F70)
 
 template <bool GN_IN, bool STATS, bool WREG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void dense_x6_kernel(DxParams p) {
@@ -115,17 +86,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int p0 = pt * DX_TP;
 
     const unsigned long long img_addr = reinterpret_cast<unsigned long long>(p.wimg) + (size_t)cb * kst * DX_ASTAGE;
-    const dx_i32x4 wsrc = {(int)(unsigned)img_addr, (int)(unsigned)(img_addr >> 32), kst * DX_ASTAGE, 0x00020000};
+    const x6_i32x4 wsrc = {(int)(unsigned)img_addr, (int)(unsigned)(img_addr >> 32), kst * DX_ASTAGE, 0x00020000};
     const unsigned lds0 = (unsigned)reinterpret_cast<size_t>((__attribute__((address_space(3))) unsigned char *)smem);
     const unsigned voff16 = lane * 16;
-    // LDS-DMA of k-step kk's weight fragments into stage st: this wave's six pieces (asm: see csrc/sa_x6.hip)
+    // LDS-DMA of k-step kk's weight fragments into stage st: this wave's six pieces (x6.h x6_lds_dma)
     auto issue_w = [&](int kk, int st) {
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             const unsigned dst = lds0 + st * DX_STAGE + (wave * 6 + i) * 1024;
             const unsigned soff = kk * DX_ASTAGE + (wave * 6 + i) * 1024;
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                         :: "s"(dst), "v"(voff16), "s"(wsrc), "s"(soff) : "memory");
+            x6_lds_dma(dst, voff16, wsrc, soff);
         }
     };
     // WREG: this wave's six weight fragments of a k-step go straight into registers -- nobody else reads them, and through LDS (two
@@ -167,7 +137,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             unsigned a0, a1, a2;
-            dx_split2(v[2 * i], v[2 * i + 1], a0, a1, a2);
+            x6_split2(v[2 * i], v[2 * i + 1], a0, a1, a2);
             f0[i] = a0; f1[i] = a1; f2[i] = a2;
         }
         unsigned char *bp = smem + st * DX_STAGE + DX_ASTAGE + wave * 3072 + lane * 16;
@@ -188,7 +158,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             v1 = relu_bits(__builtin_fmaf(c.z, v1, c.w));
         }
         unsigned a0, a1, a2;
-        dx_split2(v0, v1, a0, a1, a2);
+        x6_split2(v0, v1, a0, a1, a2);
         sf0[i] = a0; sf1[i] = a1; sf2[i] = a2;
         if constexpr (i == 3) {
             unsigned char *bp = smem + st * DX_STAGE + DX_ASTAGE + wave * 3072 + lane * 16;
@@ -230,7 +200,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int tn = 0; tn < 4; ++tn)
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) acc[tm][tn][rr] = 0.f;
-    DX_WAIT_VM(0);
+    X6_WAIT_VM(0);
     __syncthreads();
 
     // ---- k-steps ---------------------------------------------------------------------------------------------------------------
@@ -273,12 +243,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     }
                     // two position tiles' chains issued alternately (see below)
                     f32x16 a = acc[TM][tn], b = acc[TM][tn + 1];
-                    a = dx_mfma(xa[0], wr[SET][TM][2], a); b = dx_mfma(xb[0], wr[SET][TM][2], b);
-                    a = dx_mfma(xa[2], wr[SET][TM][0], a); b = dx_mfma(xb[2], wr[SET][TM][0], b);
-                    a = dx_mfma(xa[1], wr[SET][TM][1], a); b = dx_mfma(xb[1], wr[SET][TM][1], b);
-                    a = dx_mfma(xa[0], wr[SET][TM][1], a); b = dx_mfma(xb[0], wr[SET][TM][1], b);
-                    a = dx_mfma(xa[1], wr[SET][TM][0], a); b = dx_mfma(xb[1], wr[SET][TM][0], b);
-                    a = dx_mfma(xa[0], wr[SET][TM][0], a); b = dx_mfma(xb[0], wr[SET][TM][0], b);
+                    a = bf_mfma(xa[0], wr[SET][TM][2], a); b = bf_mfma(xb[0], wr[SET][TM][2], b);
+                    a = bf_mfma(xa[2], wr[SET][TM][0], a); b = bf_mfma(xb[2], wr[SET][TM][0], b);
+                    a = bf_mfma(xa[1], wr[SET][TM][1], a); b = bf_mfma(xb[1], wr[SET][TM][1], b);
+                    a = bf_mfma(xa[0], wr[SET][TM][1], a); b = bf_mfma(xb[0], wr[SET][TM][1], b);
+                    a = bf_mfma(xa[1], wr[SET][TM][0], a); b = bf_mfma(xb[1], wr[SET][TM][0], b);
+                    a = bf_mfma(xa[0], wr[SET][TM][0], a); b = bf_mfma(xb[0], wr[SET][TM][0], b);
                     acc[TM][tn] = a; acc[TM][tn + 1] = b;
                     const int kn = kk + 1 < kst ? kk + 1 : kst - 1;
                     // (the piece stays between the two MFMA groups: fragment reads, loads and scalar code may cross the fences, VALU, LDS
@@ -317,19 +287,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 // nothing sits between them (a fragment read or a staging VALU in such a chain costs ~43 cycles, between MFMAs on
                 // different accumulators ~6: MI355X_MICROARCH.md)
                 f32x16 a = acc[0][tn], b = acc[1][tn];
-                a = dx_mfma(xf[0], wf[0][2], a); b = dx_mfma(xf[0], wf[1][2], b);
-                a = dx_mfma(xf[2], wf[0][0], a); b = dx_mfma(xf[2], wf[1][0], b);
-                a = dx_mfma(xf[1], wf[0][1], a); b = dx_mfma(xf[1], wf[1][1], b);
-                a = dx_mfma(xf[0], wf[0][1], a); b = dx_mfma(xf[0], wf[1][1], b);
-                a = dx_mfma(xf[1], wf[0][0], a); b = dx_mfma(xf[1], wf[1][0], b);
-                a = dx_mfma(xf[0], wf[0][0], a); b = dx_mfma(xf[0], wf[1][0], b);
+                a = bf_mfma(xf[0], wf[0][2], a); b = bf_mfma(xf[0], wf[1][2], b);
+                a = bf_mfma(xf[2], wf[0][0], a); b = bf_mfma(xf[2], wf[1][0], b);
+                a = bf_mfma(xf[1], wf[0][1], a); b = bf_mfma(xf[1], wf[1][1], b);
+                a = bf_mfma(xf[0], wf[0][1], a); b = bf_mfma(xf[0], wf[1][1], b);
+                a = bf_mfma(xf[1], wf[0][0], a); b = bf_mfma(xf[1], wf[1][0], b);
+                a = bf_mfma(xf[0], wf[0][0], a); b = bf_mfma(xf[0], wf[1][0], b);
                 acc[0][tn] = a; acc[1][tn] = b;
             }
         }
         }
         if constexpr (!WREG) {
 #if DX_ABL != 1 && DX_ABL != 4
-            DX_WAIT_VM(0);                              // this wave's weight pieces of the next k-step have landed ...
+            X6_WAIT_VM(0);                              // this wave's weight pieces of the next k-step have landed ...
 #endif
         }
 #if DX_ABL != 4 && DX_ABL != 6

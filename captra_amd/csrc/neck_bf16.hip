@@ -87,7 +87,7 @@ __device__ __forceinline__ void nk_layer_from_image(f32x16 (&acc)[MT][2], const 
 #pragma unroll
             for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
-                for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = db_mfma(A[j & 3][tm], Bf[j & 1][tn], acc[tm][tn]);
+                for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = bf_mfma(A[j & 3][tm], Bf[j & 1][tn], acc[tm][tn]);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -108,7 +108,7 @@ __device__ __forceinline__ void nk_park(const f32x16 (&acc)[MT][2], unsigned cha
             for (int jj = 0; jj < 2; ++jj) {
                 u32x4 v;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = db_relu2(db_pack(acc[tm][tn][8 * jj + 2 * i], acc[tm][tn][8 * jj + 2 * i + 1]));
+                for (int i = 0; i < 4; ++i) v[i] = bf_relu2(bf_pack(acc[tm][tn][8 * jj + 2 * i], acc[tm][tn][8 * jj + 2 * i + 1]));
                 *reinterpret_cast<u32x4 *>(row + (((4 * t + 2 * jj + h) ^ (col & 15)) << 4)) = v;
             }
         }
@@ -207,10 +207,10 @@ __global__ __launch_bounds__(NK_NT, 1) void neck_chain_kernel(NkParams p) {
             for (int k = vw; k < p.cv; k += 16) {
                 const float xv = (float)(__bf16)vb[k];
                 const uint2 w = *reinterpret_cast<const uint2 *>(p.gw + (size_t)k * p.gldw + cc);
-                acc.x = __builtin_fmaf(__uint_as_float(w.x << 16), xv, acc.x);
-                acc.y = __builtin_fmaf(__uint_as_float(w.x & 0xffff0000u), xv, acc.y);
-                acc.z = __builtin_fmaf(__uint_as_float(w.y << 16), xv, acc.z);
-                acc.w = __builtin_fmaf(__uint_as_float(w.y & 0xffff0000u), xv, acc.w);
+                acc.x = __builtin_fmaf(bf_lo(w.x), xv, acc.x);
+                acc.y = __builtin_fmaf(bf_hi(w.x), xv, acc.y);
+                acc.z = __builtin_fmaf(bf_lo(w.y), xv, acc.z);
+                acc.w = __builtin_fmaf(bf_hi(w.y), xv, acc.w);
             }
             red[vw * 64 + lane] = acc;
         }
@@ -288,8 +288,8 @@ __global__ __launch_bounds__(NK_NT, 1) void neck_chain_kernel(NkParams p) {
                 const float a1 = r == 0 ? sf[1].x : r == 1 ? sf[1].y : r == 2 ? sf[1].z : sf[1].w;
                 const float a2 = r == 0 ? sf[2].x : r == 1 ? sf[2].y : r == 2 ? sf[2].z : sf[2].w;
                 const float a3 = r == 0 ? sf[3].x : r == 1 ? sf[3].y : r == 2 ? sf[3].z : sf[3].w;
-                v.x = db_pack(m[0] ? a0 : 0.f, m[1] ? a1 : 0.f);
-                v.y = db_pack(m[2] ? a2 : 0.f, m[3] ? a3 : 0.f);
+                v.x = bf_pack(m[0] ? a0 : 0.f, m[1] ? a1 : 0.f);
+                v.y = bf_pack(m[2] ? a2 : 0.f, m[3] ? a3 : 0.f);
             }
             *reinterpret_cast<uint2 *>(dst + pos * 256 + ((sl ^ (pos & 15)) << 4) + 8 * half) = v;
         }
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(NK_NT, 1) void neck_chain_kernel(NkParams p) {
 #pragma unroll
                     for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
-                        for (int tm = 0; tm < MT1; ++tm) acc1[tm][tn] = db_mfma(A[j & 3][tm], Bf[j & 1][tn], acc1[tm][tn]);
+                        for (int tm = 0; tm < MT1; ++tm) acc1[tm][tn] = bf_mfma(A[j & 3][tm], Bf[j & 1][tn], acc1[tm][tn]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if (j == 1 && c + 1 < nch) {                          // the next chunk: converted and parked under this chunk's MFMAs

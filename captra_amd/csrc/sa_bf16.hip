@@ -26,33 +26,14 @@
 //  * Layer 1 of the small-input scales carries its bias as two constant-one input channels (hi + lo bf16 split of b1:
 //    2^-17 relative), so its accumulators start from the inline constant 0.
 #include "common.h"
+#include "mfma_bf16.h"
 
 unsigned long long *captra_sa_prof_ptr();   // sa_fused.hip: the debug counters set by captra_sa_fused_set_prof
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int cdiv_c(int a, int b) { return (a + b - 1) / b; }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// one v_cvt_pk_bf16_f32 (the vector fptrunc; two scalar casts compile to two conversions and a v_perm_b32)
-__device__ __forceinline__ unsigned sb_pack(float lo, float hi) {
-    const f32x2 f = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-// ReLU on a packed bf16 pair
-__device__ __forceinline__ unsigned sb_relu2(unsigned v) {
-    const s16x2 z = {0, 0};
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), z));
-}
-__device__ __forceinline__ f32x16 sb_mfma(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 // max of three as ONE instruction, two forms.
 //  ASM = false: v_maximum3_f32 from llvm.maximum (no canonicalising v_max_f32 x, x, x in front as fmaxf gets in IEEE mode).
 //    The form of the kernels whose accumulators live in VGPRs: the first VALU read of an MFMA result needs software wait
@@ -109,8 +90,6 @@ struct SbPackParams {
     unsigned char *img;
 };
 
-__device__ __forceinline__ int sb_perm(int s) { return (s & 3) | ((s & 4) << 1) | ((s & 8) >> 1); }
-
 __global__ void pack_sa_bf16_kernel(SbPackParams p) {
     const int nt1 = (p.c1 + 31) / 32, nt2 = (p.c2 + 31) / 32, nt3 = (p.c3 + 31) / 32;
     const int kst2 = (p.c1 + 15) / 16, kst3 = (p.c2 + 15) / 16;
@@ -132,11 +111,11 @@ __global__ void pack_sa_bf16_kernel(SbPackParams p) {
             }
         } else if (f < f3) {
             const int t = (f - f2) / kst2, kk = (f - f2) % kst2;
-            const int row = 32 * t + (lane & 31), k = 16 * kk + sb_perm(slot);
+            const int row = 32 * t + (lane & 31), k = 16 * kk + bf_perm(slot);
             if (row < p.c2 && k < p.c1) v = p.wt2[(size_t)k * p.ldw2 + row];
         } else {
             const int t = (f - f3) / kst3, kk = (f - f3) % kst3;
-            const int row = 32 * t + (lane & 31), k = 16 * kk + sb_perm(slot);
+            const int row = 32 * t + (lane & 31), k = 16 * kk + bf_perm(slot);
             if (row < p.c3 && k < p.c2) v = p.wt3[(size_t)k * p.ldw3 + row];
         }
         const __bf16 h = (__bf16)v;
@@ -174,7 +153,7 @@ __device__ __forceinline__ void sb_mid_epilogue(const f32x16 &acc, int t, u32x4 
         if (2 * t + jj >= NOUT) continue;
         u32x4 v;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = sb_relu2(sb_pack(acc[8 * jj + 2 * i], acc[8 * jj + 2 * i + 1]));
+        for (int i = 0; i < 4; ++i) v[i] = bf_relu2(bf_pack(acc[8 * jj + 2 * i], acc[8 * jj + 2 * i + 1]));
         hout[2 * t + jj] = v;
     }
 }
@@ -322,7 +301,7 @@ __device__ __forceinline__ void sb_body(const SbParams &p, unsigned char *smem, 
             for (int i = 0; i < 4; ++i) {
                 // (not swap(g, 0): hipcc 7.2 hoists the zero register out of the pass loop although the instruction
                 // overwrites it, and the next pass swaps stale data in)
-                const unsigned g = sb_pack(in[2 * i], in[2 * i + 1]);
+                const unsigned g = bf_pack(in[2 * i], in[2 * i + 1]);
                 const auto sw = __builtin_amdgcn_permlane32_swap(g, g, false, false);     // (lo, lo), (hi, hi)
                 x1[0][i] = h ? 0u : sw[0];
                 x1[1][i] = h ? 0u : sw[1];
@@ -338,8 +317,8 @@ __device__ __forceinline__ void sb_body(const SbParams &p, unsigned char *smem, 
                 const float *cp = p.new_xyz + ((size_t)b * p.m + c) * 3;
                 const float r0 = xb[id] - cp[0], r1 = xb[(size_t)p.n + id] - cp[1], r2 = xb[(size_t)2 * p.n + id] - cp[2];
                 ids[j] = id;
-                x1[j][0] = h ? 0u : sb_pack(r0, r1);
-                x1[j][1] = h ? 0u : sb_pack(r2, 0.f);
+                x1[j][0] = h ? 0u : bf_pack(r0, r1);
+                x1[j][1] = h ? 0u : bf_pack(r2, 0.f);
                 x1[j][2] = 0u;
                 x1[j][3] = 0u;
             }
@@ -365,9 +344,9 @@ __device__ __forceinline__ void sb_body(const SbParams &p, unsigned char *smem, 
                         const float4 v = *reinterpret_cast<const float4 *>(vp + 8 * q);
                         acc[4 * q + 0] = v.x; acc[4 * q + 1] = v.y; acc[4 * q + 2] = v.z; acc[4 * q + 3] = v.w;
                     }
-                    acc = sb_mfma(w, x1[j], acc);
+                    acc = bf_mfma(w, x1[j], acc);
                 } else {
-                    acc = sb_mfma(w, x1[j], zero16);
+                    acc = bf_mfma(w, x1[j], zero16);
                 }
                 sb_mid_epilogue<S::KST2>(acc, t, h1[j]);
             }
@@ -393,7 +372,7 @@ __device__ __forceinline__ void sb_body(const SbParams &p, unsigned char *smem, 
                     if (tg + r < S::NT2) {
                         const u32x4 w = wfrag(S::F2 + (tg + r) * S::KST2 + kk);
 #pragma unroll
-                        for (int j = 0; j < TN; ++j) acc[r][j] = sb_mfma(w, h1[j][kk], kk == 0 ? bias[r] : acc[r][j]);
+                        for (int j = 0; j < TN; ++j) acc[r][j] = bf_mfma(w, h1[j][kk], kk == 0 ? bias[r] : acc[r][j]);
                     }
 #pragma unroll
             for (int r = 0; r < RG; ++r)
@@ -412,7 +391,7 @@ __device__ __forceinline__ void sb_body(const SbParams &p, unsigned char *smem, 
                     if (tg + r < S::NT3) {
                         const u32x4 w = wfrag(S::F3 + (tg + r) * S::KST3 + kk);
 #pragma unroll
-                        for (int j = 0; j < TN; ++j) acc[r][j] = sb_mfma(h2[j][kk], w, kk == 0 ? zero16 : acc[r][j]);
+                        for (int j = 0; j < TN; ++j) acc[r][j] = bf_mfma(h2[j][kk], w, kk == 0 ? zero16 : acc[r][j]);
                     }
 #pragma unroll
             for (int r = 0; r < RG; ++r)
@@ -558,8 +537,8 @@ __global__ __launch_bounds__(256, 1) void sa2_bf16_kernel(SbParams p) {
     for (int j = 0; j < TN; ++j) {
         const int id = ids[j];
         const float r0 = xb[id] - ctr[j][0], r1 = xb[(size_t)p.n + id] - ctr[j][1], r2 = xb[(size_t)2 * p.n + id] - ctr[j][2];
-        x1[j][0] = h ? 0u : sb_pack(r0, r1);
-        x1[j][1] = h ? 0u : sb_pack(r2, 0.f);
+        x1[j][0] = h ? 0u : bf_pack(r0, r1);
+        x1[j][1] = h ? 0u : bf_pack(r2, 0.f);
         x1[j][2] = 0u;
         x1[j][3] = 0u;
     }
@@ -580,7 +559,7 @@ __global__ __launch_bounds__(256, 1) void sa2_bf16_kernel(SbParams p) {
                 const float4 v = *reinterpret_cast<const float4 *>(vp + 8 * q);
                 acc[4 * q + 0] = v.x; acc[4 * q + 1] = v.y; acc[4 * q + 2] = v.z; acc[4 * q + 3] = v.w;
             }
-            acc = sb_mfma(w, x1[j], acc);
+            acc = bf_mfma(w, x1[j], acc);
             sb_mid_epilogue<S::KST2>(acc, t, h1[j]);
         }
     }
@@ -605,7 +584,7 @@ __global__ __launch_bounds__(256, 1) void sa2_bf16_kernel(SbParams p) {
     // read-out element i (0..3) of unit u = (tile u >> 1, half u & 1) of layer-2 group tg: two accumulator registers -> one packed pair
     auto epi2 = [&](int tg, int u, int i, const f32x16 (&a)[TN]) {
         const int j = u >> 1, jj = u & 1;
-        if (2 * tg + jj < S::KST3) h2[j][2 * tg + jj][i] = sb_relu2(sb_pack(a[j][8 * jj + 2 * i], a[j][8 * jj + 2 * i + 1]));
+        if (2 * tg + jj < S::KST3) h2[j][2 * tg + jj][i] = bf_relu2(bf_pack(a[j][8 * jj + 2 * i], a[j][8 * jj + 2 * i + 1]));
     };
     // the same of layer-3 group tg: two registers of tile j into the running maximum of its centre
     auto epi3 = [&](int tg, int u, int i, const f32x16 (&a)[TN]) {
@@ -621,7 +600,7 @@ __global__ __launch_bounds__(256, 1) void sa2_bf16_kernel(SbParams p) {
 #pragma unroll
             for (int j0 = 0; j0 < TN; j0 += ILV) {      // ILV MFMAs, then their ILV read-out units (ILV 1 / 2 / 4: 112.4 / 113.6 / 118.2 us at 32 clouds)
 #pragma unroll
-                for (int j = j0; j < j0 + ILV; ++j) acc[tg & 1][j] = sb_mfma(w, h1[j][kk], kk == 0 ? bv : acc[tg & 1][j]);
+                for (int j = j0; j < j0 + ILV; ++j) acc[tg & 1][j] = bf_mfma(w, h1[j][kk], kk == 0 ? bv : acc[tg & 1][j]);
 #pragma unroll
                 for (int j = j0; j < j0 + ILV; ++j)
                     if (tg > 0 && kk < 8) epi2(tg - 1, kk, j, acc[(tg - 1) & 1]);
@@ -648,7 +627,7 @@ __global__ __launch_bounds__(256, 1) void sa2_bf16_kernel(SbParams p) {
 #pragma unroll
             for (int j0 = 0; j0 < TN; j0 += ILV) {
 #pragma unroll
-                for (int j = j0; j < j0 + ILV; ++j) acc[(tg + P3) & 1][j] = sb_mfma(h2[j][kk], w, kk == 0 ? zero16 : acc[(tg + P3) & 1][j]);
+                for (int j = j0; j < j0 + ILV; ++j) acc[(tg + P3) & 1][j] = bf_mfma(h2[j][kk], w, kk == 0 ? zero16 : acc[(tg + P3) & 1][j]);
 #pragma unroll
                 for (int j = j0; j < j0 + ILV; ++j)
                     if (kk < 8) {
@@ -1321,7 +1300,7 @@ __device__ __forceinline__ void cb_layer(const unsigned char *wl, const float *b
             for (int r = 0; r < 2; ++r) {
                 const u32x4 w = *reinterpret_cast<const u32x4 *>(wl + ((tg + r) * KST + kk) * 1024 + lane * 16);
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[r][j] = sb_mfma(w, hin[j][kk], acc[r][j]);
+                for (int j = 0; j < 2; ++j) acc[r][j] = bf_mfma(w, hin[j][kk], acc[r][j]);
             }
 #pragma unroll
         for (int r = 0; r < 2; ++r)
@@ -1347,7 +1326,7 @@ __device__ __forceinline__ void cb_out_layer(const unsigned char *wl, const floa
     for (int kk = 0; kk < KST; ++kk) {
         const u32x4 w = *reinterpret_cast<const u32x4 *>(wl + kk * 1024 + lane * 16);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[j] = sb_mfma(w, hin[j][kk], acc[j]);
+        for (int j = 0; j < 2; ++j) acc[j] = bf_mfma(w, hin[j][kk], acc[j]);
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -1397,7 +1376,7 @@ __global__ __launch_bounds__(512, 2) void chain_bf16_kernel(CbParams p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xsrc, voff + (kk * 16 + i) * xrow, 0, 0));
 #pragma unroll
-            for (int i = 0; i < 4; ++i) x0[j][kk][i] = sb_pack(v[2 * i], v[2 * i + 1]);
+            for (int i = 0; i < 4; ++i) x0[j][kk][i] = bf_pack(v[2 * i], v[2 * i + 1]);
         }
     }
     u32x4 ha[2][8], hb[2][8];

@@ -3,13 +3,9 @@
 // product of the 128..256-wide layers evaluated on v_mfma_f32_32x32x16_bf16 as SIX bf16 products of a THREE-WAY split of both
 // operands, fp32 accumulation -- the opt-in arithmetic `mlp_dtype = "f32x6"`.
 //
-// Arithmetic contract (include/captra_hip.h "f32x6"): an fp32 number v is held as v = v0 + v1 + v2 EXACTLY, v0 = bf16(v),
-// v1 = bf16(v - v0), v2 = bf16(v - v0 - v1) (round to nearest even; the two residuals are exact in fp32 and the third part has at most
-// eight significant bits).  A layer is y = act(b + sum_k [w0 x0 + w0 x1 + w1 x0 + w1 x1 + w0 x2 + w2 x0]_k): the three dropped
-// products (w1 x2, w2 x1, w2 x2) are <= 2^-24 |w x| each, the kept ones are exact in the matrix pipe, the sums are fp32 -- the
-// result differs from the exact k-ascending fmaf chain (the metric's arithmetic, csrc/sa_pipe.hip) by fp32-roundoff-sized terms
-// (tests/test_x6_gpu.py: <= 2e-6 of the layer's largest output), and NOT bit for bit.  The first layer's xyz part (K = 3..6) stays on
-// v_mfma_f32_32x32x2_f32: exact, and cheaper than six padded bf16 products.
+// Arithmetic contract and the primitives shared with csrc/chain_x6.hip and csrc/dense_x6.hip: csrc/x6.h (the split, the six-product
+// group, the LDS-DMA piece, the hand-over weight image).  The first layer's xyz part (K = 3..6) stays on v_mfma_f32_32x32x2_f32: exact,
+// and cheaper than six padded bf16 products.
 //
 // Why it is its own kernel and not sa_bf16.hip with three operands: six MFMAs per k-step change the balance.
 //  * A 32-position tile's activations are 6 bytes per element: 128 + 208 channels of one tile are 252 registers, so a wave (one per
@@ -23,79 +19,26 @@
 //    over the neighbours is 8 v_max3 per tile), bias and ReLU after the max.
 //  * every epilogue is deferred by one tile and spread over the next tile's k-steps behind its MFMAs.
 #include "common.h"
-#include <type_traits>
+#include "x6.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void sx_lds_void;
-typedef const __attribute__((address_space(1))) void sx_glb_void;
-
-constexpr int sx_cdiv(int a, int b) { return (a + b - 1) / b; }
-constexpr int sx_pad4(int a) { return (a + 3) / 4 * 4; }
 constexpr int sx_max(int a, int b) { return a > b ? a : b; }
 constexpr int sx_pad128(int c) { return (c + 127) / 128 * 128; }
 
-__device__ __forceinline__ unsigned sx_pack(float lo, float hi) {          // one v_cvt_pk_bf16_f32 (RNE)
-    const f32x2 f = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-__device__ __forceinline__ float sx_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float sx_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-
-// (a, b) -> the packed pairs of their three parts
-__device__ __forceinline__ void sx_split2(float a, float b, unsigned &p0, unsigned &p1, unsigned &p2) {
-    p0 = sx_pack(a, b);
-    const float ra = a - sx_lo(p0), rb = b - sx_hi(p0);
-    p1 = sx_pack(ra, rb);
-    p2 = sx_pack(ra - sx_lo(p1), rb - sx_hi(p1));
-}
-
-__device__ __forceinline__ f32x16 sx_mfma(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// the six products of one k-step as TWO accumulator chains issued alternately -- `lo` takes the three small products (2^-16 of the
-// leading one), `hi` the three large ones; a tile's result is hi + lo.  Back-to-back MFMAs on ONE accumulator run at the issue rate only
-// while nothing sits between them: every ds_read / VALU the scheduler puts into such a chain costs ~43 cycles (MI355X_MICROARCH.md),
-// and a k-step carries three fragment reads -- one chain ran the matrix pipe at 0.62-0.68; between MFMAs on different accumulators a
-// filler costs ~6.  FLIP: activations are the A operand (rows = positions)
-template <bool FLIP>
-__device__ __forceinline__ void sx_group(f32x16 &hi, f32x16 &lo, const u32x4 (&w)[3], const u32x4 &x0, const u32x4 &x1, const u32x4 &x2) {
-    if constexpr (FLIP) {
-        lo = sx_mfma(x0, w[2], lo); hi = sx_mfma(x0, w[1], hi); lo = sx_mfma(x2, w[0], lo);
-        hi = sx_mfma(x1, w[0], hi); lo = sx_mfma(x1, w[1], lo); hi = sx_mfma(x0, w[0], hi);
-    } else {
-        lo = sx_mfma(w[2], x0, lo); hi = sx_mfma(w[1], x0, hi); lo = sx_mfma(w[0], x2, lo);
-        hi = sx_mfma(w[0], x1, hi); lo = sx_mfma(w[1], x1, lo); hi = sx_mfma(w[0], x0, hi);
-    }
-}
 __device__ __forceinline__ float sx_max3(float a, float b, float c) {
     return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
-}
-
-// compile-time loop: f(std::integral_constant<int, I>) for I in [0, N) -- the body sees I as a constant expression (the
-// scheduling-group builtins want integer constants)
-template <int I, int N, typename F>
-__device__ __forceinline__ void sx_static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        sx_static_for<I + 1, N>(f);
-    }
 }
 
 template <int CF, int C1, int C2, int C3, bool PRE>
 struct SxShape {
     static constexpr int CIN1 = CF + 3;
-    static constexpr int KS1 = PRE ? 2 : sx_cdiv(CF + 3, 2);        // fp32 k-steps (two rows each) of the first layer's MFMA part
-    static constexpr int NT1 = sx_cdiv(C1, 32), NT2 = sx_cdiv(C2, 32), NT3 = sx_cdiv(C3, 32);
-    static constexpr int KST2 = sx_cdiv(C1, 16), KST3 = sx_cdiv(C2, 16);
+    static constexpr int KS1 = PRE ? 2 : x6_cdiv(CF + 3, 2);        // fp32 k-steps (two rows each) of the first layer's MFMA part
+    static constexpr int NT1 = x6_cdiv(C1, 32), NT2 = x6_cdiv(C2, 32), NT3 = x6_cdiv(C3, 32);
+    static constexpr int KST2 = x6_cdiv(C1, 16), KST3 = x6_cdiv(C2, 16);
     // a CHUNK = one row tile of layer 2 / 3: its k-steps' fragment triples (k-step major: fragment 3 kk + part), padded to a
     // multiple of four fragments so that every wave of a workgroup issues the same number of LDS-DMA pieces
-    static constexpr int CH2 = sx_pad4(KST2 * 3), CH3 = sx_pad4(KST3 * 3);
+    static constexpr int CH2 = x6_pad4(KST2 * 3), CH3 = x6_pad4(KST3 * 3);
     static constexpr int NCH = NT2 + NT3;
     static constexpr int WBYTES = (NT2 * CH2 + NT3 * CH3) * 1024;
     static constexpr int SLOTB = sx_max(CH2, CH3) * 1024;
@@ -106,46 +49,23 @@ struct SxShape {
 };
 
 // ---- image builder ----------------------------------------------------------------------------------------------------------
-// One thread per bf16 element of the fragment part, then the biases.  wt2 / wt3: packed fp32 W'^T, row-major part (element
-// [k * ldw + cout]).  Fragment (chunk, kk, part): lane l = row 32 t + (l & 31), k-slots 8 (l >> 5) .. + 7 of k-step kk, slot s
-// holding channel 16 kk + perm(s) (sa_bf16.hip's hand-over order).
+// One thread per bf16 element of the fragment part (layer 2's block, then layer 3's, both in the hand-over order: x6.h
+// x6_frag_bits), then the biases.  wt2 / wt3: packed fp32 W'^T, row-major part (element [k * ldw + cout]).
 struct SxPackParams {
     int c1, c2, c3, ldw2, ldw3;
     const float *b1, *wt2, *b2, *wt3, *b3;
     unsigned char *img;
 };
 
-__device__ __forceinline__ int sx_perm(int s) { return (s & 3) | ((s & 4) << 1) | ((s & 8) >> 1); }
-
 __global__ void pack_sa_x6_kernel(SxPackParams p) {
-    const int nt1 = (p.c1 + 31) / 32, nt2 = (p.c2 + 31) / 32, nt3 = (p.c3 + 31) / 32;
-    const int kst2 = (p.c1 + 15) / 16, kst3 = (p.c2 + 15) / 16;
-    const int ch2 = (kst2 * 3 + 3) / 4 * 4, ch3 = (kst3 * 3 + 3) / 4 * 4;
+    const int nt1 = x6_cdiv(p.c1, 32), nt2 = x6_cdiv(p.c2, 32), nt3 = x6_cdiv(p.c3, 32);
+    const int ch2 = x6_pad4(x6_cdiv(p.c1, 16) * 3), ch3 = x6_pad4(x6_cdiv(p.c2, 16) * 3);
     const int nfrag = nt2 * ch2 + nt3 * ch3;
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < (long long)nfrag * 512) {
-        const int f = (int)(e >> 9), lane = (int)(e >> 3) & 63, el = (int)e & 7;
-        const int slot = 8 * (lane >> 5) + el;
-        float v = 0.f;
-        int part = 0;
-        if (f < nt2 * ch2) {
-            const int t = f / ch2, r = f % ch2, kk = r / 3;
-            part = r % 3;
-            const int row = 32 * t + (lane & 31), k = 16 * kk + sx_perm(slot);
-            if (kk < kst2 && row < p.c2 && k < p.c1) v = p.wt2[(size_t)k * p.ldw2 + row];
-        } else {
-            const int g = f - nt2 * ch2;
-            const int t = g / ch3, r = g % ch3, kk = r / 3;
-            part = r % 3;
-            const int row = 32 * t + (lane & 31), k = 16 * kk + sx_perm(slot);
-            if (kk < kst3 && row < p.c3 && k < p.c2) v = p.wt3[(size_t)k * p.ldw3 + row];
-        }
-        const __bf16 h0 = (__bf16)v;
-        const float r1 = v - (float)h0;
-        const __bf16 h1 = (__bf16)r1;
-        const __bf16 h2 = (__bf16)(r1 - (float)h1);
-        const __bf16 h = part == 0 ? h0 : (part == 1 ? h1 : h2);
-        reinterpret_cast<unsigned short *>(p.img)[e] = __builtin_bit_cast(unsigned short, h);
+        const long long e3 = e - (long long)nt2 * ch2 * 512;       // >= 0: layer 3's block
+        reinterpret_cast<unsigned short *>(p.img)[e] = e3 < 0 ? x6_frag_bits(e, p.c1, p.c2, p.ldw2, false, p.wt2)
+                                                              : x6_frag_bits(e3, p.c2, p.c3, p.ldw3, false, p.wt3);
     } else {
         const int i = (int)(e - (long long)nfrag * 512);
         const int nb = (nt1 + nt2 + nt3) * 32;
@@ -174,9 +94,6 @@ struct SxParams {
     int out_ctotal, co_off;
 };
 
-// s_waitcnt with only the vector-memory counter set (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14)
-#define SX_WAIT_VM(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | (((N) >> 4) << 14) | 0x0F70)
-
 // ReLU + three-way split of unit u (k-step half jj = u >> 2, register pair i = u & 3) of output tile t -> hout[part][2 t + jj][i]
 template <int KSTN>
 __device__ __forceinline__ void sx_split_unit(const f32x16 &acc, int t, int u, u32x4 (&hout)[3][KSTN]) {
@@ -184,24 +101,19 @@ __device__ __forceinline__ void sx_split_unit(const f32x16 &acc, int t, int u, u
     if (2 * t + jj >= KSTN) return;
     const float a = relu_bits(acc[8 * jj + 2 * i]), b = relu_bits(acc[8 * jj + 2 * i + 1]);
     unsigned p0, p1, p2;
-    sx_split2(a, b, p0, p1, p2);
-    // pin the unit HERE: left alone, LLVM sinks the whole split (pure arithmetic) down to its first use -- the next layer's first
-    // MFMA -- five tiles' worth of it end up in one block that no MFMA covers and their accumulators stay live until then (the
-    // 196-wide scale spills); the scheduling barriers around a group do not bind IR-level sinking, an asm statement that
-    // "modifies" the three results does.  (With ONE accumulator chain per tile the pinned units cost more than they hid: 384 -> 453 us.)
+    x6_split2(a, b, p0, p1, p2);
+    // pinned HERE (x6.h "the split": why, and where the other kernels pin).  (With ONE accumulator chain per tile the pinned units
+    // cost more than they hid: 384 -> 453 us.)
     asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2));
     hout[0][2 * t + jj][i] = p0;
     hout[1][2 * t + jj][i] = p1;
     hout[2][2 * t + jj][i] = p2;
 }
 
-// the group of the NEXT tile's k-steps behind whose MFMAs unit u (0..7) of a deferred split epilogue is issued: none in group 0
-// (the tile's last MFMA is still executing), spread over groups 1 .. KST - 1
-constexpr int sx_unit_group(int u, int kst) { return kst > 1 ? 1 + u * (kst - 1) / 8 : 0; }
 // layer 2's LAST tile may be read out under layer 3's first tile when every unit precedes the k-step that consumes it
 constexpr bool sx_defer_last_ok(int nt2, int kst3) {
     for (int u = 0; u < 8; ++u)
-        if (2 * (nt2 - 1) + (u >> 2) < kst3 && sx_unit_group(u, kst3) > 2 * (nt2 - 1) + (u >> 2)) return false;
+        if (2 * (nt2 - 1) + (u >> 2) < kst3 && x6_unit_group(u, kst3) > 2 * (nt2 - 1) + (u >> 2)) return false;
     return kst3 > 1;
 }
 
@@ -210,9 +122,9 @@ constexpr int sx_group_valu(bool l3, int t, int kk, int nt2, int kst2, int kst3,
     int n = 0;
     if (!l3 && t == 0 && kk + 1 >= 2 && kk + 1 < kst2) n += 52;
     if (!l3 && t > 0)
-        for (int u = 0; u < 8; ++u) n += sx_unit_group(u, kst2) == kk ? 13 : 0;
+        for (int u = 0; u < 8; ++u) n += x6_unit_group(u, kst2) == kk ? 13 : 0;
     if (l3 && t == 0 && defer_last)
-        for (int u = 0; u < 8; ++u) n += sx_unit_group(u, kst3) == kk ? 13 : 0;
+        for (int u = 0; u < 8; ++u) n += x6_unit_group(u, kst3) == kk ? 13 : 0;
     if (l3 && t > 0 && kk == (kst3 > 1 ? 1 : 0)) n += 8;
     return n;
 }
@@ -229,31 +141,18 @@ __device__ __forceinline__ void sx_body(const SxParams &p, unsigned char *smem) 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, col = lane & 31;
 
-    // LDS-DMA of chunk c (static) into its slot: this wave's quarter of the fragments
-    // The pieces are issued as asm statements: hipcc (ROCm 7.2) orders every LDS read it can see behind ALL LDS-DMA in flight
-    // (s_waitcnt vmcnt(0) in front of the first ds_read after an issue -- the bias reads of the next tile: the prefetch would wait for
-    // itself), and it keeps a 64-bit per-lane address per piece of the global form and spills them.  Buffer form: one VGPR of lane
-    // offsets, the piece's place in the image as a scalar offset; m0 = the piece's LDS byte address (wave-uniform; the hardware adds
-    // lane x 16).  The compiler's own vmcnt waits stay safe: loads return in order, pieces it does not know of only make it wait longer.
-    typedef int sx_i32x4 __attribute__((ext_vector_type(4)));
+    // LDS-DMA of chunk c (static) into its slot: this wave's quarter of the fragments (x6.h x6_ring_issue)
     const unsigned long long img_addr = reinterpret_cast<unsigned long long>(p.img);
-    const sx_i32x4 wsrc = {(int)(unsigned)img_addr, (int)(unsigned)(img_addr >> 32), S::WBYTES, 0x00020000};
+    const x6_i32x4 wsrc = {(int)(unsigned)img_addr, (int)(unsigned)(img_addr >> 32), S::WBYTES, 0x00020000};
     const unsigned lds0 = (unsigned)reinterpret_cast<size_t>((__attribute__((address_space(3))) unsigned char *)smem);
     const unsigned voff16 = lane * 16;
-    auto issue_chunk = [&](int c) {
-        const unsigned dst = lds0 + (c % NS) * S::SLOTB + wave * 1024;
-        const unsigned soff = S::chunk_off(c) + wave * 1024;
-#pragma unroll
-        for (int i = 0; i < S::chunk_frags(c) / 4; ++i)
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                         :: "s"(dst + i * 4096), "v"(voff16), "s"(wsrc), "s"(soff + i * 4096) : "memory");
-    };
+    auto issue_chunk = [&](int c) { x6_ring_issue(lds0 + (c % NS) * S::SLOTB, voff16, wsrc, S::chunk_off(c), wave, S::chunk_frags(c)); };
     // chunk c becomes readable (and chunk c + 1 goes on its way into the slot chunk c - 2 left: every wave is past that chunk's
     // last MFMA when it arrives here, so no LDS wait is needed in front of the barrier)
     auto acquire = [&](int c) {
         if constexpr (RING) {
 #if !defined(CAPTRA_SX_ABL) || CAPTRA_SX_ABL < 2          // (timing ablations, results wrong: 1 = no LDS-DMA after start-up, 2 = no barrier either)
-            SX_WAIT_VM(0);
+            X6_WAIT_VM(0);
             __builtin_amdgcn_s_barrier();
 #endif
 #if !defined(CAPTRA_SX_ABL) || CAPTRA_SX_ABL < 1
@@ -287,7 +186,7 @@ __device__ __forceinline__ void sx_body(const SxParams &p, unsigned char *smem) 
                 at[j][t] = (ok && 32 * t + col < C1) ? p.w1[(size_t)row * LDW1 + 32 * t + col] : 0.f;
             }
     }
-    if constexpr (RING) SX_WAIT_VM(0);                                      // chunk 0 landed (this wave's pieces) ...
+    if constexpr (RING) X6_WAIT_VM(0);                                      // chunk 0 landed (this wave's pieces) ...
     __syncthreads();                                                       // ... and everybody's; biases / the resident image visible
     if constexpr (RING) issue_chunk(1);
 
@@ -415,7 +314,7 @@ __device__ __forceinline__ void sx_body(const SxParams &p, unsigned char *smem) 
 
         // ---- layers 2 and 3: G groups of six MFMAs; tile tau accumulates in acc[tau & 1], tile tau - 1 is read out behind them ------
         f32x16 acc[2], accl[2];                         // (hi, lo) chains of tile tau in acc[tau & 1], accl[tau & 1]; merged into acc at read-out
-        sx_static_for<0, G>([&](auto gi_c) __attribute__((always_inline)) {
+        x6_static_for<0, G>([&](auto gi_c) __attribute__((always_inline)) {
             constexpr int gi = decltype(gi_c)::value;
             constexpr bool l3 = gi >= G2;
             constexpr int t = l3 ? (gi - G2) / S::KST3 : gi / S::KST2;
@@ -466,20 +365,20 @@ __device__ __forceinline__ void sx_body(const SxParams &p, unsigned char *smem) 
             if constexpr (!l3 && t > 0) {
 #pragma unroll
                 for (int u = 0; u < 8; ++u)
-                    if (sx_unit_group(u, S::KST2) == kk) { sx_split_unit<S::KST3>(acc[(tau - 1) & 1], t - 1, u, h2); }
+                    if (x6_unit_group(u, S::KST2) == kk) { sx_split_unit<S::KST3>(acc[(tau - 1) & 1], t - 1, u, h2); }
             }
             if constexpr (l3 && t == 0 && DEFER_LAST) {
 #pragma unroll
                 for (int u = 0; u < 8; ++u)
-                    if (sx_unit_group(u, S::KST3) == kk) { sx_split_unit<S::KST3>(acc[(tau - 1) & 1], S::NT2 - 1, u, h2); }
+                    if (x6_unit_group(u, S::KST3) == kk) { sx_split_unit<S::KST3>(acc[(tau - 1) & 1], S::NT2 - 1, u, h2); }
             }
             if constexpr (l3 && t > 0 && kk == (S::KST3 > 1 ? 1 : 0)) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) z[t - 1] = sx_max3(z[t - 1], acc[(tau - 1) & 1][2 * i], acc[(tau - 1) & 1][2 * i + 1]);
             }
             // ---- the six products ----
-            if (!l3) sx_group<false>(acc[tau & 1], accl[tau & 1], wr[gi & 1], h1[0][kk], h1[1][kk], h1[2][kk]);
-            else sx_group<true>(acc[tau & 1], accl[tau & 1], wr[gi & 1], h2[0][kk], h2[1][kk], h2[2][kk]);
+            if (!l3) x6_group<false>(acc[tau & 1], accl[tau & 1], wr[gi & 1], h1[0][kk], h1[1][kk], h1[2][kk]);
+            else x6_group<true>(acc[tau & 1], accl[tau & 1], wr[gi & 1], h2[0][kk], h2[1][kk], h2[2][kk]);
             // one MFMA, then a sixth of the group's VALU work: each of them issues while an MFMA executes
             {
                 constexpr int per = (sx_group_valu(l3, t, kk, S::NT2, S::KST2, S::KST3, DEFER_LAST) + 5) / 6;
@@ -522,7 +421,7 @@ __device__ __forceinline__ void sx_body(const SxParams &p, unsigned char *smem) 
         job = jobn; sl = sn; c = cn_raw; ce = cn;
     }
     // nothing of the ring may land in LDS after the workgroup is gone
-    if constexpr (RING) SX_WAIT_VM(0);
+    if constexpr (RING) X6_WAIT_VM(0);
 }
 
 template <int CF, int C1, int C2, int C3, bool PRE, bool RING, int WAVES>
@@ -550,8 +449,8 @@ int sx_launch(const SxParams &p, hipStream_t stream) {
 
 extern "C" long long captra_sa_x6_image_bytes(int cfeat, int c1, int c2, int c3) {
     if (cfeat < 0 || c1 < 1 || c2 < 1 || c3 < 1) return -1;
-    const long long nt1 = (c1 + 31) / 32, nt2 = (c2 + 31) / 32, nt3 = (c3 + 31) / 32;
-    const long long ch2 = (((c1 + 15) / 16) * 3 + 3) / 4 * 4, ch3 = (((c2 + 15) / 16) * 3 + 3) / 4 * 4;
+    const long long nt1 = x6_cdiv(c1, 32), nt2 = x6_cdiv(c2, 32), nt3 = x6_cdiv(c3, 32);
+    const long long ch2 = x6_pad4(x6_cdiv(c1, 16) * 3), ch3 = x6_pad4(x6_cdiv(c2, 16) * 3);
     return (nt2 * ch2 + nt3 * ch3) * 1024 + (nt1 + nt2 + nt3) * 32 * 4;
 }
 

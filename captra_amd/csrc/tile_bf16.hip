@@ -52,8 +52,8 @@ __device__ __forceinline__ u32x4 tb_affine(u32x4 v, const float (&a)[8], const f
     u32x4 r;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float lo = __uint_as_float(v[i] << 16), hi = __uint_as_float(v[i] & 0xffff0000u);
-        r[i] = db_relu2(db_pack(__builtin_fmaf(lo, a[2 * i], b[2 * i]), __builtin_fmaf(hi, a[2 * i + 1], b[2 * i + 1])));
+        const float lo = bf_lo(v[i]), hi = bf_hi(v[i]);
+        r[i] = bf_relu2(bf_pack(__builtin_fmaf(lo, a[2 * i], b[2 * i]), __builtin_fmaf(hi, a[2 * i + 1], b[2 * i + 1])));
     }
     return r;
 }
@@ -65,8 +65,8 @@ __device__ __forceinline__ void tb_store_tile(const f32x16 &acc, unsigned char *
         u32x4 v;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            v[i] = db_pack(acc[8 * jj + 2 * i], acc[8 * jj + 2 * i + 1]);
-            if (relu) v[i] = db_relu2(v[i]);
+            v[i] = bf_pack(acc[8 * jj + 2 * i], acc[8 * jj + 2 * i + 1]);
+            if (relu) v[i] = bf_relu2(v[i]);
         }
         *reinterpret_cast<u32x4 *>(yrow + 32 * jj) = v;
     }
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(NW * 64, 2) void tb_layer_kernel(TbParams p) {
         const float *abp = p.ab + (size_t)b * p.cin * 2;
         for (int e = tid; e < kst * 32; e += NT) {
             const int kk = e >> 5, hh = (e >> 4) & 1, i = e & 15;
-            const int c = 16 * kk + db_perm(8 * hh + (i & 7));
+            const int c = 16 * kk + bf_perm(8 * hh + (i & 7));
             aff_tab[e] = c < p.cin ? abp[2 * c + (i >> 3)] : 0.f;
         }
     }
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(NW * 64, 2) void tb_layer_kernel(TbParams p) {
                     for (int q = 0; q < 4; ++q) {
                         const float lo = r == 0 ? sf[i][2 * q].x : r == 1 ? sf[i][2 * q].y : r == 2 ? sf[i][2 * q].z : sf[i][2 * q].w;
                         const float hi = r == 0 ? sf[i][2 * q + 1].x : r == 1 ? sf[i][2 * q + 1].y : r == 2 ? sf[i][2 * q + 1].z : sf[i][2 * q + 1].w;
-                        v[q] = db_pack(m[2 * q] != 0.f ? lo : 0.f, m[2 * q + 1] != 0.f ? hi : 0.f);
+                        v[q] = bf_pack(m[2 * q] != 0.f ? lo : 0.f, m[2 * q + 1] != 0.f ? hi : 0.f);
                     }
                     *reinterpret_cast<u32x4 *>(dst + pos * 256 + ((sl ^ (pos & 15)) << 4)) = v;
                 }
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(NW * 64, 2) void tb_layer_kernel(TbParams p) {
 #pragma unroll
                 for (int tn = 0; tn < TB_TN; ++tn)
 #pragma unroll
-                    for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = db_mfma(A[j & 3][tm], Bf[j & 1][tn], acc[tm][tn]);
+                    for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = bf_mfma(A[j & 3][tm], Bf[j & 1][tn], acc[tm][tn]);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (j == 1 && c + 1 < nch) {                              // the next chunk: transform + park under this chunk's MFMAs
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(512, 2) void tb_head12_kernel(HbParams p) {
 #pragma unroll
                 for (int tn = 0; tn < TB_TN; ++tn)
 #pragma unroll
-                    for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = db_mfma(A[j & 3][tm], Bf[j & 1][tn], acc[tm][tn]);
+                    for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = bf_mfma(A[j & 3][tm], Bf[j & 1][tn], acc[tm][tn]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(512, 2) void tb_head12_kernel(HbParams p) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int r = 8 * jj + 2 * i;
-                        v[i] = db_relu2(db_pack(__builtin_fmaf(acc[tm][tn][r], ca[r], cb[r]), __builtin_fmaf(acc[tm][tn][r + 1], ca[r + 1], cb[r + 1])));
+                        v[i] = bf_relu2(bf_pack(__builtin_fmaf(acc[tm][tn][r], ca[r], cb[r]), __builtin_fmaf(acc[tm][tn][r + 1], ca[r + 1], cb[r + 1])));
                     }
                     *reinterpret_cast<u32x4 *>(row + (((4 * t + 2 * jj + h) ^ (col & 15)) << 4)) = v;
                 }
@@ -466,7 +466,7 @@ __global__ __launch_bounds__(512, 2) void tb_head12_kernel(HbParams p) {
 #pragma unroll
                 for (int tn = 0; tn < TB_TN; ++tn)
 #pragma unroll
-                    for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = db_mfma(A[j & 3][tm], Bf[j & 1][tn], acc[tm][tn]);
+                    for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = bf_mfma(A[j & 3][tm], Bf[j & 1][tn], acc[tm][tn]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -591,7 +591,7 @@ __global__ __launch_bounds__(512, 2) void tb_head12p_kernel(HpParams pp) {
 #pragma unroll
                     for (int tn = 0; tn < TB_TN; ++tn)
 #pragma unroll
-                        for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = db_mfma(A[j & 3][tm], Bf[tn], acc[tm][tn]);
+                        for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = bf_mfma(A[j & 3][tm], Bf[tn], acc[tm][tn]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -620,7 +620,7 @@ __global__ __launch_bounds__(512, 2) void tb_head12p_kernel(HpParams pp) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int r = 8 * jj + 2 * i;
-                        v[i] = db_relu2(db_pack(__builtin_fmaf(acc[tm][tn][r], ca[r], cb[r]), __builtin_fmaf(acc[tm][tn][r + 1], ca[r + 1], cb[r + 1])));
+                        v[i] = bf_relu2(bf_pack(__builtin_fmaf(acc[tm][tn][r], ca[r], cb[r]), __builtin_fmaf(acc[tm][tn][r + 1], ca[r + 1], cb[r + 1])));
                     }
                     *reinterpret_cast<u32x4 *>(row + (((4 * t + 2 * jj + h) ^ (col & 15)) << 4)) = v;
                 }
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(512, 2) void tb_head12p_kernel(HpParams pp) {
 #pragma unroll
                 for (int tn = 0; tn < TB_TN; ++tn)
 #pragma unroll
-                    for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = db_mfma(A[j & 3][tm], Bf[tn], acc[tm][tn]);
+                    for (int tm = 0; tm < MT; ++tm) acc[tm][tn] = bf_mfma(A[j & 3][tm], Bf[tn], acc[tm][tn]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }

@@ -1129,7 +1129,6 @@ def chain_x6_image(layers) -> torch.Tensor:
         nl = len(layers)
         cin = (C.c_int * nl)(*[lin.cin for lin in layers])
         cout = (C.c_int * nl)(*[lin.cout for lin in layers])
-        L.lib().captra_chain_x6_image_bytes.restype = C.c_longlong
         nbytes = L.lib().captra_chain_x6_image_bytes(nl, cin, cout)
         frag_total = nbytes - nl * 128 * 4
         img = torch.empty(nbytes, dtype=torch.uint8, device=layers[0].wt.device)
