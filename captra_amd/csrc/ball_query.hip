@@ -29,6 +29,7 @@
 //     once per cloud by its own launch into a caller-provided workspace (an ABI addition) and candidates read from L2.
 // Distance: ((cx-x)^2 + (cy-y)^2) + (cz-z)^2, unfused fp32, strict '<' against radius*radius.
 #include "common.h"
+#include "wave_ops.h"
 #include "bq_scan.h"
 
 namespace {
@@ -116,12 +117,7 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void ball_query_kernel(int n, int m,
                 }
             }
 #pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) {
-                    lo[a] = fminf(lo[a], __shfl_xor(lo[a], off, 64));
-                    hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off, 64));
-                }
+            for (int a = 0; a < 3; ++a) WAVE_BUTTERFLY2(lo[a], fminf, hi[a], fmaxf, 32)
             if (lane == 0) {
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {

@@ -136,23 +136,6 @@ __device__ __forceinline__ float dist2_unfused(float ax, float ay, float az, flo
     return (xx + yy) + zz;
 }
 
-// 64-bit shuffle helpers (wave64)
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int mask) {
-    unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
-    lo = __shfl_xor(lo, mask, 64);
-    hi = __shfl_xor(hi, mask, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        unsigned long long o = shfl_xor_u64(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // activation codes of the shared-MLP entry points (include/captra_hip.h: CAPTRA_ACT_*)
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID_M05 = 2 };
 

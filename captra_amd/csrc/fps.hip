@@ -17,41 +17,6 @@
 
 namespace {
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_mov(unsigned v) {
-    // lanes whose source is invalid / masked keep their own value (old = v)
-    return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
-
-// reductions over a row of 16 lanes: afterwards every lane of the row holds the row result
-__device__ __forceinline__ unsigned row_max_u32(unsigned v) {
-    v = max(v, dpp_mov<0xB1, 0xF>(v));   // quad_perm [1,0,3,2]
-    v = max(v, dpp_mov<0x4E, 0xF>(v));   // quad_perm [2,3,0,1]
-    v = max(v, dpp_mov<0x141, 0xF>(v));  // row_half_mirror
-    v = max(v, dpp_mov<0x140, 0xF>(v));  // row_mirror
-    return v;
-}
-__device__ __forceinline__ unsigned row_min_u32(unsigned v) {
-    v = min(v, dpp_mov<0xB1, 0xF>(v));
-    v = min(v, dpp_mov<0x4E, 0xF>(v));
-    v = min(v, dpp_mov<0x141, 0xF>(v));
-    v = min(v, dpp_mov<0x140, 0xF>(v));
-    return v;
-}
-// full wave64 reductions, result returned wave-uniform (SGPR)
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-    v = row_max_u32(v);
-    v = max(v, dpp_mov<0x142, 0xA>(v));  // row_bcast15 -> rows 1,3
-    v = max(v, dpp_mov<0x143, 0xC>(v));  // row_bcast31 -> rows 2,3
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-    v = row_min_u32(v);
-    v = min(v, dpp_mov<0x142, 0xA>(v));
-    v = min(v, dpp_mov<0x143, 0xC>(v));
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-
 // NWAVES: waves per workgroup (power of two <= 16); PPT: points held per lane;
 // XYZ_LDS: whole cloud mirrored in LDS (SoA) for the broadcast read of the last pick.
 template <int NWAVES, int PPT, bool XYZ_LDS>

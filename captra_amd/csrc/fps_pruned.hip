@@ -41,41 +41,13 @@
 // 3.47 -> 3.09 ms, 16384 -> 2048 1.53 -> 1.46 ms on surface-like clouds; uniform clouds -2 .. -7 %, except 16384 uniform
 // points (+6 %: every slot of every wave in use, and a round now waits for the wave with the most buckets to update).
 #include "common.h"
+#include "wave_ops.h"
 #include <type_traits>
 
 namespace {
 
 constexpr int FP_BINS = 4096;       // 16 x 16 x 16 Morton cells
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned fp_dpp_max(unsigned v) {   // 0 is the identity: invalid sources contribute 0
-    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
-    return max(v, o);
-}
-__device__ __forceinline__ unsigned fp_row_max(unsigned v) {
-    v = fp_dpp_max<0xB1, 0xF>(v);
-    v = fp_dpp_max<0x4E, 0xF>(v);
-    v = fp_dpp_max<0x141, 0xF>(v);
-    v = fp_dpp_max<0x140, 0xF>(v);
-    return v;
-}
-__device__ __forceinline__ unsigned fp_wave_max(unsigned v) {
-    v = fp_row_max(v);
-    v = fp_dpp_max<0x142, 0xA>(v);
-    v = fp_dpp_max<0x143, 0xC>(v);
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ unsigned fp_wave_min(unsigned v) { return ~fp_wave_max(~v); }
-__device__ __forceinline__ float fp_wave_minf(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float fp_wave_maxf(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
 __device__ __forceinline__ float fp_readlane(float v, int l) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
 }
@@ -143,8 +115,8 @@ __global__ __launch_bounds__(FP_NW * 64) void fps_pruned_kernel(int n_stride, co
         lx = fminf(lx, x); ly = fminf(ly, y); lz = fminf(lz, z);
         hx = fmaxf(hx, x); hy = fmaxf(hy, y); hz = fmaxf(hz, z);
     }
-    lx = fp_wave_minf(lx); ly = fp_wave_minf(ly); lz = fp_wave_minf(lz);
-    hx = fp_wave_maxf(hx); hy = fp_wave_maxf(hy); hz = fp_wave_maxf(hz);
+    lx = wave_minf(lx); ly = wave_minf(ly); lz = wave_minf(lz);
+    hx = wave_maxf(hx); hy = wave_maxf(hy); hz = wave_maxf(hz);
     if (lane == 0) {
         red[0 * 16 + wave] = lx; red[1 * 16 + wave] = ly; red[2 * 16 + wave] = lz;
         red[3 * 16 + wave] = hx; red[4 * 16 + wave] = hy; red[5 * 16 + wave] = hz;
@@ -258,8 +230,8 @@ __global__ __launch_bounds__(FP_NW * 64) void fps_pruned_kernel(int n_stride, co
         if (B == 0 || s < A) dmin.set(s, __uint_as_float(dnew));
         else o[192] = __uint_as_float(dnew);
         if (first) {   // the bucket's bounding box (once)
-            const float a0 = fp_wave_minf(x), a1 = fp_wave_minf(y), a2 = fp_wave_minf(z);
-            const float b0 = fp_wave_maxf(x), b1 = fp_wave_maxf(y), b2 = fp_wave_maxf(z);
+            const float a0 = wave_minf(x), a1 = wave_minf(y), a2 = wave_minf(z);
+            const float b0 = wave_maxf(x), b1 = wave_maxf(y), b2 = wave_maxf(z);
             if (lane == s) { blx = a0; bly = a1; blz = a2; bhx = b0; bhy = b1; bhz = b2; }
         } else {
             // the bucket's maximum (and who holds it) can only change if a point AT the maximum was lowered
@@ -267,18 +239,18 @@ __global__ __launch_bounds__(FP_NW * 64) void fps_pruned_kernel(int n_stride, co
             if (__ballot(dnew != dold && dold == bm_old) == 0ull) return;
         }
         ++n_ref;
-        const unsigned bm = fp_wave_max(dnew);
+        const unsigned bm = wave_max_u32_fold(dnew);
         const unsigned long long hit = __ballot(dnew == bm);
         int wl = __ffsll((long long)hit) - 1;
         const int q0 = (s * FP_NW + wave) << 6;
         const unsigned oi = (unsigned)oidx[q0 + lane];
         if (hit & (hit - 1)) {   // the maximum is attained more than once: lowest ORIGINAL index wins
-            const unsigned best = fp_wave_min((dnew == bm) ? oi : 0xFFFFFFFFu);
+            const unsigned best = wave_min_u32_fold((dnew == bm) ? oi : 0xFFFFFFFFu);
             wl = __ffsll((long long)__ballot(dnew == bm && oi == best)) - 1;
         }
         const float wx = fp_readlane(x, wl), wy = fp_readlane(y, wl), wz = fp_readlane(z, wl);
         const unsigned woi = (unsigned)__builtin_amdgcn_readlane((int)oi, wl);
-        const unsigned ru = fp_wave_max(lane == wl ? 0u : dnew);      // the rest of the bucket never exceeds this
+        const unsigned ru = wave_max_u32_fold(lane == wl ? 0u : dnew);      // the rest of the bucket never exceeds this
         if (lane == s) { bmax = bm; boi = woi; bwx = wx; bwy = wy; bwz = wz; brun = ru; }
     };
     // test every bucket of the wave against the pending samples (same operations as the point distance: fl(p - o), squares,
@@ -318,14 +290,14 @@ __global__ __launch_bounds__(FP_NW * 64) void fps_pruned_kernel(int n_stride, co
         const unsigned long long t1 = STATS ? __builtin_amdgcn_s_memtime() : 0ull;
         // the wave's candidate (its largest bucket maximum, lowest original index among equals) and its obstacle: nothing
         // else this wave holds exceeds max(second-largest bucket maximum, runner-up bound of the candidate's bucket)
-        const unsigned wm = fp_wave_max(bmax);
+        const unsigned wm = wave_max_u32_fold(bmax);
         const unsigned long long hitb = __ballot(bmax == wm);
         int li = __ffsll((long long)hitb) - 1;
         if (hitb & (hitb - 1)) {
-            const unsigned best = fp_wave_min((bmax == wm) ? boi : 0xFFFFFFFFu);
+            const unsigned best = wave_min_u32_fold((bmax == wm) ? boi : 0xFFFFFFFFu);
             li = __ffsll((long long)__ballot(bmax == wm && boi == best)) - 1;
         }
-        const unsigned second = fp_wave_max(lane == li ? 0u : bmax);
+        const unsigned second = wave_max_u32_fold(lane == li ? 0u : bmax);
         const unsigned topru = (unsigned)__builtin_amdgcn_readlane((int)brun, li);
         const unsigned obst = second > topru ? second : topru;
         uint2 *slot = slots + (rounds & 1) * 16;

@@ -5,29 +5,9 @@
 // strict '>' arg max = lowest index among equal maxima.
 #pragma once
 #include "common.h"
+#include "wave_ops.h"
 
 typedef float fps_f32x2 __attribute__((ext_vector_type(2)));
-
-// u32 max reductions whose DPP move folds into the max (v_max_u32_dpp): 0 is the identity, so lanes without a valid
-// source (bound_ctrl) or in masked-off rows simply contribute 0
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_max_u32(unsigned v) {
-    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
-    return max(v, o);
-}
-__device__ __forceinline__ unsigned row_max_u32_fold(unsigned v) {
-    v = dpp_max_u32<0xB1, 0xF>(v);
-    v = dpp_max_u32<0x4E, 0xF>(v);
-    v = dpp_max_u32<0x141, 0xF>(v);
-    v = dpp_max_u32<0x140, 0xF>(v);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max_u32_fold(unsigned v) {
-    v = row_max_u32_fold(v);
-    v = dpp_max_u32<0x142, 0xA>(v);  // row_bcast15 -> rows 1,3
-    v = dpp_max_u32<0x143, 0xC>(v);  // row_bcast31 -> rows 2,3
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
 
 // A lane's sixteen points against the last pick (ox, oy, oz): running minima updated (on the bit patterns: distances are >= 0),
 // `best` = the largest of them, `li` = its lowest slot -- the maximum through a tree of pairwise maxima, the slot as a descent

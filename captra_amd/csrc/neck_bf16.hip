@@ -14,6 +14,7 @@
 // Per layer the MFMA sequence, the bf16 roundings and the activation are tb_layer_kernel's: outputs are bit-identical to the
 // layer-by-layer route (tests/test_neck_gpu.py).
 #include "common.h"
+#include "wave_ops.h"
 #include "bf16_dense.h"
 
 namespace {
@@ -148,8 +149,7 @@ __device__ __forceinline__ void nk_epilogue(const f32x16 (&acc)[MT][2], const Nk
                 mx[r] = -INFINITY;
 #pragma unroll
                 for (int tn = 0; tn < 2; ++tn) mx[r] = pos0 + tn * 32 + col < p.L ? fmaxf(mx[r], acc[tm][tn][r]) : mx[r];
-#pragma unroll
-                for (int off = 16; off >= 1; off >>= 1) mx[r] = fmaxf(mx[r], __shfl_xor(mx[r], off, 64));
+                WAVE_BUTTERFLY(mx[r], 16, fmaxf);
             }
             if (col == 0) {
                 int *yp = reinterpret_cast<int *>(p.y) + (size_t)b * ly.cout + row0;

@@ -29,6 +29,7 @@
 // Pipeline: register-staged prefetch (global loads of chunk c+1 are issued before the MFMAs of
 // chunk c and written to LDS after them), 2 workgroups per CU.
 #include "common.h"
+#include "wave_ops.h"
 #include <atomic>
 #include <type_traits>
 
@@ -70,19 +71,6 @@ struct PwParams {
     int csplit, x2_bcast;
     int dbg;              // CAPTRA_ABLATIONS builds only (timing ablations of the direct kernel, results wrong; != 0 takes the general epilogue): 1 = no y stores, 2 = no statistics, 4 = every workgroup reads the first columns, 8 = one statistics store per row tile
 };
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-// max over each row of 16 lanes, result in every lane of the row
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, dpp_f<0xB1>(v));
-    v = fmaxf(v, dpp_f<0x4E>(v));
-    v = fmaxf(v, dpp_f<0x141>(v));
-    v = fmaxf(v, dpp_f<0x140>(v));
-    return v;
-}
 
 // BM x BN output tile per workgroup, 4 waves arranged WGM x WGN, wave tile (TM*32) x (TN*32).
 template <int BM, int BN, int WGM, int WGN, int PRO, int EPI, bool VECX>
@@ -273,7 +261,7 @@ __global__ __launch_bounds__(PW_THREADS) void pw_mlp_kernel(PwParams p) {
                 for (int r = 0; r < 16; ++r) {
                     float v = acc[tm][tn][r];
                     v = (v > 0.f && col_ok) ? v : 0.f;  // ReLU (the only activation followed by a max in the path)
-                    v = row16_max(v);
+                    v = row16_maxf(v);
                     v = fmaxf(v, __shfl_xor(v, 16, 64));
                     if ((lane & 31) == 0) {
                         const int rl = (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
@@ -330,20 +318,7 @@ int launch_pw(int b, const PwParams &p, hipStream_t s, const char *name) {
 // ST:  the epilogue also reduces this layer's raw output to per-row, per-64-column-tile (sum, sum of squares)
 //      partials -- fixed DPP order, no atomics -- from which captra_gn_finalize derives the next coefficients.
 // Together they remove the separate GroupNorm pass (one read and one write of the activation tensor per layer).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add_f32(float v) {  // 0 is the identity: lanes without a source / masked rows add 0
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, true));
-}
-// sum over each half-wave (32 lanes): valid in lanes 16..31 (lower half) and 48..63 (upper half)
-__device__ __forceinline__ float half_wave_sum(float v) {
-    v = dpp_add_f32<0xB1, 0xF>(v);
-    v = dpp_add_f32<0x4E, 0xF>(v);
-    v = dpp_add_f32<0x141, 0xF>(v);
-    v = dpp_add_f32<0x140, 0xF>(v);   // every lane of a row of 16 holds the row sum
-    v = dpp_add_f32<0x142, 0xA>(v);   // row_bcast15: rows 1 and 3 add rows 0 and 2
-    return v;
-}
-
+// (the statistics' half-wave sums: half_wave_sum, wave_ops.h)
 // Transposing reduction of the statistics epilogue: 16 per-row values per lane -> ONE value per lane, the total over the half-wave's
 // 32 lanes of the row the lane stands for.  Each step halves the registers: a lane keeps the first of a register pair where its lane
 // bit is 0 and the second where it is 1, and adds its partner's copy of the one it keeps.  Bits 2 and 3 pick whole banks of four
@@ -351,14 +326,14 @@ __device__ __forceinline__ float half_wave_sum(float v) {
 // instructions instead of 16 five-step butterflies, and one store per lane at the end instead of two two-lane stores per row.
 template <int CTRL_LO, int CTRL_HI, int BANK_LO, int BANK_HI>
 __device__ __forceinline__ float xchg_add_banked(float a, float b) {
-    const int x = __builtin_amdgcn_update_dpp(__float_as_int(b), __float_as_int(a), CTRL_LO, 0xF, BANK_LO, false);   // bit 0 lanes: the partner's a
-    const int y = __builtin_amdgcn_update_dpp(__float_as_int(a), __float_as_int(b), CTRL_HI, 0xF, BANK_HI, false);   // bit 1 lanes: the partner's b
-    return __int_as_float(x) + __int_as_float(y);
+    const float x = dpp_keep<CTRL_LO, 0xF, BANK_LO>(b, a);   // bit 0 lanes: the partner's a
+    const float y = dpp_keep<CTRL_HI, 0xF, BANK_HI>(a, b);   // bit 1 lanes: the partner's b
+    return x + y;
 }
 template <int CTRL>
 __device__ __forceinline__ float xchg_add_select(float a, float b, bool bit) {
     const float keep = bit ? b : a, send = bit ? a : b;
-    return keep + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(send), CTRL, 0xF, 0xF, true));
+    return keep + dpp_zero<CTRL>(send);
 }
 // v[16] -> the half-wave total of register rr(lane) = ((lane >> 1) & 1) + 2 (lane & 1) + 4 ((lane >> 3) & 1) + 8 ((lane >> 2) & 1)
 __device__ __forceinline__ float half_wave_transpose_sum(const float (&v)[16], int lane) {
@@ -775,16 +750,13 @@ __global__ __launch_bounds__(256) void pw_direct_max_kernel(PwParams p) {
         const int xbits = __float_as_int(acc[r]);
         v[r] = (xbits > 0 && col_ok) ? xbits : 0;       // ReLU on the bit pattern; columns beyond L contribute 0
     }
-#define PM_STEP(CTRL)                                                                                   \
-    _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                   \
-        const int o = __builtin_amdgcn_update_dpp(0, v[r], CTRL, 0xF, 0xF, true);                       \
-        v[r] = o > v[r] ? o : v[r];                                                                     \
-    }
+#define PM_STEP(CTRL) \
+    _Pragma("unroll") for (int r = 0; r < 16; ++r) v[r] = imax_dpp<CTRL>(v[r], v[r]);     // (v >= 0: 0 is the identity)
     PM_STEP(0xB1) PM_STEP(0x4E) PM_STEP(0x141) PM_STEP(0x140)
 #undef PM_STEP
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int o = __builtin_amdgcn_update_dpp(v[r], v[r], 0x142, 0xA, 0xF, false);  // row_bcast15 into rows 1, 3
+        const int o = dpp_keep<0x142, 0xA>(v[r]);  // row_bcast15 into rows 1, 3
         v[r] = o > v[r] ? o : v[r];
     }
     if ((lane & 31) == 16) {
@@ -834,11 +806,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(int nb, int c, int cpg
             sq += (double)v.y;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        sm += __shfl_xor(sm, off, 64);
-        sq += __shfl_xor(sq, off, 64);
-    }
+    WAVE_BUTTERFLY2(sm, wave_add, sq, wave_add, 32)
     const double cnt = (double)cpg * (double)n;
     const double mean = sm / cnt;
     double var = sq / cnt - mean * mean;

@@ -21,31 +21,13 @@
 #include "common.h"
 #include "pose_solve.h"
 #include "rot_pool.h"
+#include "wave_ops.h"
 
 #include <math.h>
 
 namespace {
 
 constexpr int PF_THREADS = 256;
-
-template <int NV>
-__device__ __forceinline__ void block_reduce_sum(double (&v)[NV], double *smem /* [NV][4] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        double x = v[i];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-        v[i] = x;
-    }
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) smem[i * 4 + wave] = v[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = (smem[i * 4 + 0] + smem[i * 4 + 1]) + (smem[i * 4 + 2] + smem[i * 4 + 3]);
-}
 
 __global__ __launch_bounds__(PF_THREADS) void part_fit_st_kernel(int p, int n, int sym, int tgt_per_part,
                                                                  const int *__restrict__ labels,
@@ -86,7 +68,7 @@ __global__ __launch_bounds__(PF_THREADS) void part_fit_st_kernel(int p, int n, i
         }
     }
     double r1[7] = {fc, fs[0], fs[1], fs[2], ft[0], ft[1], ft[2]};
-    block_reduce_sum<7>(r1, smem);
+    wg_sum<WG_SUM_PAIRS, 4>(r1, smem);
     const double cnt = r1[0];
     const double den = cnt > 1.0 ? cnt : 1.0;
     const double sb[3] = {r1[1] / den, r1[2] / den, r1[3] / den};
@@ -122,56 +104,16 @@ __global__ __launch_bounds__(PF_THREADS) void part_fit_st_kernel(int p, int n, i
     for (int i = 0; i < 9; ++i) r2[i] = fC[i];
 #pragma unroll
     for (int i = 0; i < 6; ++i) r2[9 + i] = fS[i];
-    block_reduce_sum<15>(r2, smem);
+    wg_sum<WG_SUM_PAIRS, 4>(r2, smem);
 
     if (tid == 0) {
         double R[9], Rf[9];
         for (int i = 0; i < 9; ++i) Rf[i] = R[i] = rot[(size_t)q * 9 + i];
-        if (sym) {
-            // M (2x2) = (x,z) block of R^T C
-            double M[4];
-            const int ax[2] = {0, 2};
-            for (int i = 0; i < 2; ++i)
-                for (int j = 0; j < 2; ++j) {
-                    double acc = 0;
-                    for (int k = 0; k < 3; ++k) acc += R[k * 3 + ax[i]] * r2[k * 3 + ax[j]];
-                    M[i * 2 + j] = acc;
-                }
-            const double a = M[0] + M[3], c = M[2] - M[1];
-            const double h = sqrt(a * a + c * c);
-            double cs = 1.0, sn = 0.0;
-            if (h > 0.0) {
-                cs = a / h;
-                sn = c / h;
-            } else if (h != h) {
-                cs = sn = NAN;
-            }
-            const double R3[9] = {cs, 0, -sn, 0, 1, 0, sn, 0, cs};
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j) {
-                    double acc = 0;
-                    for (int k = 0; k < 3; ++k) acc += R[i * 3 + k] * R3[k * 3 + j];
-                    Rf[i * 3 + j] = acc;
-                }
-        }
-        // numerator <R', C>; denominator sum |R'(s - sb)|^2 = <R'^T R', Css> with the actual R'
-        // (the reference rotates first, then squares, so a non-orthonormal R' is honoured)
-        double num = 0;
-        for (int i = 0; i < 9; ++i) num += Rf[i] * r2[i];
-        const double Css[9] = {r2[9], r2[10], r2[11], r2[10], r2[12], r2[13], r2[11], r2[13], r2[14]};
-        double dn = 0;
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double g = 0;  // (R'^T R')_ij
-                for (int k = 0; k < 3; ++k) g += Rf[k * 3 + i] * Rf[k * 3 + j];
-                dn += g * Css[i * 3 + j];
-            }
-        const double sca = given_scale ? (double)given_scale[q] : num / (dn + 1e-6);
+        if (sym) ps_rot_about_y(R, r2, Rf);       // R' = R embed_y(the 2-D fit)
+        const double sca = given_scale ? (double)given_scale[q] : ps_scale(Rf, r2, r2 + 9);
         double tr[3];
-        for (int a = 0; a < 3; ++a) {
-            const double rs = Rf[a * 3] * sb[0] + Rf[a * 3 + 1] * sb[1] + Rf[a * 3 + 2] * sb[2];
-            tr[a] = cnt > 0.0 ? (tb[a] - sca * rs) : 0.0;
-        }
+        ps_trans(Rf, sca, sb, tb, tr);
+        for (int a = 0; a < 3; ++a) tr[a] = cnt > 0.0 ? tr[a] : 0.0;
         const float scf = (float)sca;
         const float trf[3] = {(float)tr[0], (float)tr[1], (float)tr[2]};
         double rsum = 0;
@@ -200,7 +142,7 @@ __global__ __launch_bounds__(PF_THREADS) void procrustes_rot3_kernel(int n, cons
 #pragma unroll
             for (int c = 0; c < 3; ++c) m[a * 3 + c] += (double)T[(size_t)i * 3 + a] * (double)S[(size_t)i * 3 + c];
     }
-    block_reduce_sum<9>(m, smem);
+    wg_sum<WG_SUM_PAIRS, 4>(m, smem);
     if (threadIdx.x == 0) {
         double R[9];
         kabsch3(m, R);

@@ -8,7 +8,7 @@
 //   2. check: every member's squared fp32 residual under the tracked pose's twelve parameters (fp32(scale rot), trans), by the
 //      one inlier test of the RANSAC fit (pose_solve.h); inliers counted by ballot + population count (integers: any order gives
 //      the same sum), their squared residuals summed in double (each thread its members in ascending order, then the fixed tree
-//      of rs_block_sum); the members are read through the list, once each -- nothing is staged for a part that is not lost;
+//      of the workgroup sum, wave_ops.h); the members are read through the list, once each -- nothing is staged for a part that is not lost;
 //   3. verdict from integers alone: count < min_members, inliers * D < L * count;
 //   4. only for a lost part with refit = 1: the coordinates into LDS and the RANSAC fit's own stages (pose_ransac.h, the same
 //      device functions as captra_part_fit_ransac: same members, same draws with b0 + b in the key, same bits); accepted when it
@@ -38,22 +38,10 @@ __global__ __launch_bounds__(RS_THREADS) void part_fit_guard_kernel(int p, int n
     const int q = blockIdx.x;
     const int bi = q / p, pi = q % p;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned short *idx = reinterpret_cast<unsigned short *>(rs_dyn);
-    float *co = reinterpret_cast<float *>(rs_dyn + ((n * 2 + 15) / 16) * 16);
-
-    RsMembers mem;
-    mem.S = src + (size_t)q * 3 * n;
-    mem.T = pts + (size_t)bi * 3 * n;
-    mem.n = n;
-    mem.has_tm = pts_mean != nullptr;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) mem.tm[a] = pts_mean ? pts_mean[bi * 3 + a] : 0.f;
-    mem.in_lds = false;
-    mem.idx = idx;
-    mem.co = co;
+    RsMembers mem = rs_members(src + (size_t)q * 3 * n, pts + (size_t)bi * 3 * n, n, pts_mean, bi, rs_dyn);
 
     // ---- 1. members
-    const int count = rs_list_members(labels + (size_t)bi * n, pi, n, idx, lds.wcnt);
+    const int count = rs_list_members(labels + (size_t)bi * n, pi, n, mem.idx, lds.wcnt);
 
     // ---- 2. the tracked pose against them
     using Test = RsTest<SYM>;
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(RS_THREADS) void part_fit_guard_kernel(int p, int n
         if (in) sq[0] += (double)e2;
     }
     if (lane == 0) lds.wcnt[wave] = mine;
-    rs_block_sum<1>(sq, lds.red);                               // (its barriers also publish wcnt)
+    wg_sum<WG_SUM_SERIAL, RS_WAVES>(sq, lds.red);                             // (its barriers also publish wcnt)
     int inliers = 0;
 #pragma unroll
     for (int w = 0; w < RS_WAVES; ++w) inliers += lds.wcnt[w];
@@ -102,7 +90,7 @@ __global__ __launch_bounds__(RS_THREADS) void part_fit_guard_kernel(int p, int n
     // ---- 4. re-fit of a lost part
     RsResult res;
     if (refit && verdict == GUARD_LOST) {       // (uniform)
-        rs_stage_members(mem, count, co);
+        rs_stage_members(mem, count);
         rs_fit<SYM>(mem, count, q, b0 + bi, pi, num_hyps, th, nullptr, seed, nullptr, lds, res);
     }
 

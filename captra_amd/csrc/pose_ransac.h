@@ -8,6 +8,7 @@
 #pragma once
 #include "common.h"
 #include "pose_solve.h"
+#include "wave_ops.h"
 
 #include <math.h>
 
@@ -35,30 +36,6 @@ struct RsLds {
     int best;
 };
 
-template <int NV>
-__device__ __forceinline__ void rs_block_sum(double (&v)[NV], double *smem /* [NV][RS_WAVES] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        double x = v[i];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-        v[i] = x;
-    }
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) smem[i * RS_WAVES + wave] = v[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        double x = 0.0;
-#pragma unroll
-        for (int w = 0; w < RS_WAVES; ++w) x += smem[i * RS_WAVES + w];
-        v[i] = x;
-    }
-}
-
 // splitmix64's finaliser: the draw generator of captra_part_fit_ransac (include/captra_hip.h)
 __device__ __forceinline__ unsigned long long rs_mix(unsigned long long z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -77,8 +54,8 @@ struct RsMembers {
     int n;
     float tm[3];
     bool has_tm, in_lds;
-    const unsigned short *idx;       // LDS: point index of member m
-    const float *co;                 // LDS: [6][n] src xyz, tgt xyz of member m (in_lds)
+    unsigned short *idx;             // LDS: point index of member m
+    float *co;                       // LDS: [6][n] src xyz, tgt xyz of member m (in_lds)
     __device__ __forceinline__ void load(int m, float s[3], float t[3]) const {
         if (in_lds) {
 #pragma unroll
@@ -97,6 +74,24 @@ struct RsMembers {
         }
     }
 };
+
+// The members of one (b, p) from a kernel's arguments: S / T its source and target rows, tgt_mean (B,3) or NULL, dyn the kernel's
+// dynamic LDS (the index list, then the coordinates); nothing is staged yet (rs_stage_members)
+__device__ __forceinline__ RsMembers rs_members(const float *S, const float *T, int n, const float *tgt_mean, int bi, unsigned char *dyn) {
+    unsigned short *idx = reinterpret_cast<unsigned short *>(dyn);
+    float *co = reinterpret_cast<float *>(dyn + ((n * 2 + 15) / 16) * 16);
+    RsMembers mem;
+    mem.S = S;
+    mem.T = T;
+    mem.n = n;
+    mem.has_tm = tgt_mean != nullptr;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) mem.tm[a] = tgt_mean ? tgt_mean[bi * 3 + a] : 0.f;
+    mem.in_lds = false;
+    mem.idx = idx;
+    mem.co = co;
+    return mem;
+}
 
 // The members of part pi among lab[0..n), in ascending point index, into idx; -> their number (uniform over the workgroup).
 __device__ __forceinline__ int rs_list_members(const int *__restrict__ lab, int pi, int n, unsigned short *idx, int *s_wcnt) {
@@ -123,10 +118,10 @@ __device__ __forceinline__ int rs_list_members(const int *__restrict__ lab, int 
 }
 
 // The members' coordinates into LDS (N <= RS_LDS_N; mem.in_lds says which regime holds afterwards).  Ends with a barrier.
-__device__ __forceinline__ void rs_stage_members(RsMembers &mem, int count, float *co) {
+__device__ __forceinline__ void rs_stage_members(RsMembers &mem, int count) {
     const int n = mem.n;
+    float *co = mem.co;
     mem.in_lds = n <= RS_LDS_N;
-    mem.co = co;
     if (mem.in_lds) {
         for (int m = threadIdx.x; m < count; m += RS_THREADS) {
             const int i = mem.idx[m];
@@ -141,24 +136,25 @@ __device__ __forceinline__ void rs_stage_members(RsMembers &mem, int count, floa
     __syncthreads();
 }
 
+// The first best hypothesis: the largest score, then the smallest h (num_hyps <= 512, scores < 2^22).  One whole wave calls it; every
+// lane gets the answer.
+__device__ __forceinline__ int rs_first_best(const int *score, int num_hyps) {
+    int key = -1;
+    for (int h = (int)(threadIdx.x & 63); h < num_hyps; h += 64) {
+        const int k = (score[h] << 9) | (511 - h);
+        key = k > key ? k : key;
+    }
+    WAVE_BUTTERFLY(key, 32, imax);
+    return 511 - (key & 511);
+}
+
 // Umeyama from the centred moments: M[a][c] = sum tc_a sc_c, Css = sum sc sc^T (xx xy xz yy yz zz), centroids sb / tb
 //   R = kabsch3(M); s = <R, M> / (<R^T R, Css> + 1e-6) = sum (R sc).tc / (sum |R sc|^2 + 1e-6); t = tb - s R sb = mean(tgt - s R src)
 __device__ void rs_umeyama(const double M[9], const double C6[6], const double sb[3], const double tb[3], double R[9], double *sc_out,
                            double tr[3]) {
     kabsch3(M, R);
-    double num = 0;
-    for (int i = 0; i < 9; ++i) num += R[i] * M[i];
-    const double Css[9] = {C6[0], C6[1], C6[2], C6[1], C6[3], C6[4], C6[2], C6[4], C6[5]};
-    double dn = 0;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double g = 0;
-            for (int k = 0; k < 3; ++k) g += R[k * 3 + i] * R[k * 3 + j];
-            dn += g * Css[i * 3 + j];
-        }
-    const double sca = num / (dn + 1e-6);
-    for (int a = 0; a < 3; ++a) tr[a] = tb[a] - sca * (R[a * 3] * sb[0] + R[a * 3 + 1] * sb[1] + R[a * 3 + 2] * sb[2]);
-    *sc_out = sca;
+    *sc_out = ps_scale(R, M, C6);
+    ps_trans(R, *sc_out, sb, tb, tr);
 }
 
 // The SOLVER of rs_fit: what turns the centred moments of a set of pairs (three members, or the winner's inliers) into a pose.
@@ -171,53 +167,16 @@ struct RsUmeyama {
 };
 
 // RsGivenRot: the rotation R0 is GIVEN (the workgroup's), scale and translation are fitted -- the algebra of part_fit_st_kernel
-// (pose_fit.hip) on the same moments: SYM finds the in-plane rotation about y from the (x,z) block of R0^T M by atan2 (h = 0: identity;
-// a NaN propagates) and R = R0 embed_y; s = <R, M> / (<R^T R, Css> + 1e-6), honouring a non-orthonormal R; t = tb - s R sb.
+// (pose_fit.hip) on the same moments, by the same functions (pose_solve.h): SYM takes the in-plane rotation about y first.
 template <bool SYM>
 struct RsGivenRot {
     double R0[9];
     __device__ void operator()(const double M[9], const double C6[6], const double sb[3], const double tb[3], double R[9], double *sc_out,
                                double tr[3]) const {
-        for (int i = 0; i < 9; ++i) R[i] = R0[i];
-        if constexpr (SYM) {
-            double M2[4];
-            const int ax[2] = {0, 2};
-            for (int i = 0; i < 2; ++i)
-                for (int j = 0; j < 2; ++j) {
-                    double acc = 0;
-                    for (int k = 0; k < 3; ++k) acc += R0[k * 3 + ax[i]] * M[k * 3 + ax[j]];
-                    M2[i * 2 + j] = acc;
-                }
-            const double a = M2[0] + M2[3], c = M2[2] - M2[1];
-            const double h = sqrt(a * a + c * c);
-            double cs = 1.0, sn = 0.0;
-            if (h > 0.0) {
-                cs = a / h;
-                sn = c / h;
-            } else if (h != h) {
-                cs = sn = NAN;
-            }
-            const double R3[9] = {cs, 0, -sn, 0, 1, 0, sn, 0, cs};
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j) {
-                    double acc = 0;
-                    for (int k = 0; k < 3; ++k) acc += R0[i * 3 + k] * R3[k * 3 + j];
-                    R[i * 3 + j] = acc;
-                }
-        }
-        double num = 0;
-        for (int i = 0; i < 9; ++i) num += R[i] * M[i];
-        const double Css[9] = {C6[0], C6[1], C6[2], C6[1], C6[3], C6[4], C6[2], C6[4], C6[5]};
-        double dn = 0;
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double g = 0;
-                for (int k = 0; k < 3; ++k) g += R[k * 3 + i] * R[k * 3 + j];
-                dn += g * Css[i * 3 + j];
-            }
-        const double sca = num / (dn + 1e-6);
-        for (int a = 0; a < 3; ++a) tr[a] = tb[a] - sca * (R[a * 3] * sb[0] + R[a * 3 + 1] * sb[1] + R[a * 3 + 2] * sb[2]);
-        *sc_out = sca;
+        if constexpr (SYM) ps_rot_about_y(R0, M, R);
+        else for (int i = 0; i < 9; ++i) R[i] = R0[i];
+        *sc_out = ps_scale(R, M, C6);
+        ps_trans(R, *sc_out, sb, tb, tr);
     }
 };
 
@@ -334,17 +293,8 @@ __device__ __forceinline__ void rs_fit(const RsMembers &mem, int count, int q, i
 
         // ---- 4. the first best hypothesis (largest score, then smallest h), and the refit on its inliers
         if (wave == 0) {
-            int key = -1;
-            for (int h = lane; h < num_hyps; h += 64) {
-                const int k = (L.score[h] << 9) | (511 - h);
-                key = k > key ? k : key;
-            }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const int o = __shfl_xor(key, off, 64);
-                key = o > key ? o : key;
-            }
-            if (lane == 0) L.best = 511 - (key & 511);
+            const int best = rs_first_best(L.score, num_hyps);
+            if (lane == 0) L.best = best;
         }
         __syncthreads();
         res.best = L.best;
@@ -367,7 +317,7 @@ __device__ __forceinline__ void rs_fit(const RsMembers &mem, int count, int q, i
                     }
                 }
             }
-            rs_block_sum<7>(r1, L.red);
+            wg_sum<WG_SUM_SERIAL, RS_WAVES>(r1, L.red);
             const double cnt = r1[0];
             const double sb[3] = {r1[1] / cnt, r1[2] / cnt, r1[3] / cnt}, tb[3] = {r1[4] / cnt, r1[5] / cnt, r1[6] / cnt};
             double r2[15];
@@ -391,7 +341,7 @@ __device__ __forceinline__ void rs_fit(const RsMembers &mem, int count, int q, i
                     r2[12] += sc[1] * sc[1]; r2[13] += sc[1] * sc[2]; r2[14] += sc[2] * sc[2];
                 }
             }
-            rs_block_sum<15>(r2, L.red);
+            wg_sum<WG_SUM_SERIAL, RS_WAVES>(r2, L.red);
             if (tid == 0) {
                 double R[9], sca, tr[3];
                 solve(r2, r2 + 9, sb, tb, R, &sca, tr);

@@ -37,20 +37,10 @@ __global__ __launch_bounds__(RS_THREADS) void part_fit_ransac_kernel(int p, int 
 
     const int q = blockIdx.x;
     const int bi = q / p, pi = q % p;
-    unsigned short *idx = reinterpret_cast<unsigned short *>(rs_dyn);
-    float *co = reinterpret_cast<float *>(rs_dyn + ((n * 2 + 15) / 16) * 16);
+    RsMembers mem = rs_members(src + (size_t)q * 3 * n, tgt + (size_t)(tgt_per_part ? q : bi) * 3 * n, n, tgt_mean, bi, rs_dyn);
 
-    RsMembers mem;
-    mem.S = src + (size_t)q * 3 * n;
-    mem.T = tgt + (size_t)(tgt_per_part ? q : bi) * 3 * n;
-    mem.n = n;
-    mem.has_tm = tgt_mean != nullptr;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) mem.tm[a] = tgt_mean ? tgt_mean[bi * 3 + a] : 0.f;
-    mem.idx = idx;
-
-    const int count = rs_list_members(labels + (size_t)bi * n, pi, n, idx, lds.wcnt);      // 1. (pose_ransac.h)
-    rs_stage_members(mem, count, co);
+    const int count = rs_list_members(labels + (size_t)bi * n, pi, n, mem.idx, lds.wcnt);  // 1. (pose_ransac.h)
+    rs_stage_members(mem, count);
     RsResult res;
     rs_fit<SYM>(mem, count, q, bi, pi, num_hyps, th, sample_rank, seed, samples_out, lds, res);  // 2.-4.
 

@@ -1,6 +1,7 @@
 // The 3x3 orthogonal Procrustes solve shared by pose_fit.hip (captra_procrustes_rot3) and the RANSAC fit (pose_ransac.h:
 // captra_part_fit_ransac, captra_part_fit_guard): double-precision cyclic Jacobi on M^T M, and the rotation
-// U diag(1,1,det(UV^T)) V^T read off its eigenvectors.  And the ONE inlier test of the RANSAC fit and the track guard.
+// U diag(1,1,det(UV^T)) V^T read off its eigenvectors.  The ONE inlier test of the RANSAC fit and the track guard.  And the scale /
+// translation algebra under a known rotation (ps_*), shared by part_fit_st_kernel, rs_umeyama and RsGivenRot.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -48,6 +49,56 @@ struct RsTest {
         else return rs_inlier(s, t, hp, th2);
     }
 };
+
+// ---- the scale / translation algebra of a fit whose rotation is known (pose_fit.hip's header), in double, on the centred moments
+// M[a][c] = sum tc_a sc_c and C6 = sum sc sc^T (xx xy xz yy yz zz) and the centroids sb / tb.
+// The in-plane rotation about y of the symmetric categories: the 2-D fit on the (x,z) block of R0^T M is the rotation by
+// atan2(M10 - M01, M00 + M11) (h = 0: the identity; a NaN propagates); R = R0 embed_y(that)
+static __device__ __forceinline__ void ps_rot_about_y(const double R0[9], const double M[9], double R[9]) {
+    double M2[4];
+    const int ax[2] = {0, 2};
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j) {
+            double acc = 0;
+            for (int k = 0; k < 3; ++k) acc += R0[k * 3 + ax[i]] * M[k * 3 + ax[j]];
+            M2[i * 2 + j] = acc;
+        }
+    const double a = M2[0] + M2[3], c = M2[2] - M2[1];
+    const double h = sqrt(a * a + c * c);
+    double cs = 1.0, sn = 0.0;
+    if (h > 0.0) {
+        cs = a / h;
+        sn = c / h;
+    } else if (h != h) {
+        cs = sn = NAN;
+    }
+    const double R3[9] = {cs, 0, -sn, 0, 1, 0, sn, 0, cs};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double acc = 0;
+            for (int k = 0; k < 3; ++k) acc += R0[i * 3 + k] * R3[k * 3 + j];
+            R[i * 3 + j] = acc;
+        }
+}
+// s = <R, M> / (<R^T R, Css> + 1e-6) = sum (R sc).tc / (sum |R sc|^2 + 1e-6): the denominator with the actual R (the reference rotates
+// first, then squares, so a non-orthonormal R is honoured)
+static __device__ __forceinline__ double ps_scale(const double R[9], const double M[9], const double C6[6]) {
+    double num = 0;
+    for (int i = 0; i < 9; ++i) num += R[i] * M[i];
+    const double Css[9] = {C6[0], C6[1], C6[2], C6[1], C6[3], C6[4], C6[2], C6[4], C6[5]};
+    double dn = 0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double g = 0;  // (R^T R)_ij
+            for (int k = 0; k < 3; ++k) g += R[k * 3 + i] * R[k * 3 + j];
+            dn += g * Css[i * 3 + j];
+        }
+    return num / (dn + 1e-6);
+}
+// t = tb - s R sb = mean(tgt - s R src)
+static __device__ __forceinline__ void ps_trans(const double R[9], double s, const double sb[3], const double tb[3], double tr[3]) {
+    for (int a = 0; a < 3; ++a) tr[a] = tb[a] - s * (R[a * 3] * sb[0] + R[a * 3 + 1] * sb[1] + R[a * 3 + 2] * sb[2]);
+}
 
 static __device__ void jacobi_eig3(double A[9], double V[9]) {
     for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;

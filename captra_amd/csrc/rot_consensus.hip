@@ -124,17 +124,8 @@ __global__ __launch_bounds__(RS_THREADS) void rot_pool_consensus_kernel(int p, i
 
         // ---- 4. the first best hypothesis (largest score, then smallest h)
         if (wave == 0) {
-            int key = -1;
-            for (int h = lane; h < num_hyps; h += 64) {
-                const int k = (L.score[h] << 9) | (511 - h);
-                key = k > key ? k : key;
-            }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const int o = __shfl_xor(key, off, 64);
-                key = o > key ? o : key;
-            }
-            if (lane == 0) L.best = 511 - (key & 511);
+            const int best = rs_first_best(L.score, num_hyps);
+            if (lane == 0) L.best = best;
         }
         __syncthreads();
     }

@@ -4,6 +4,7 @@
 // the same set of pooled points gives the same bits whichever kernel pooled it.
 #pragma once
 #include "common.h"
+#include "wave_ops.h"
 
 #include <math.h>
 
@@ -82,23 +83,10 @@ __device__ __forceinline__ void rp_pool_compose(int q, int pi, int n, int sym, c
             acc[6] += in ? (double)v[2] : 0.0; acc[7] += in ? (double)v[5] : 0.0; acc[8] += in ? (double)v[8] : 0.0;
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        double x = acc[i];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-        acc[i] = x;
-    }
-    __syncthreads();
-    if (lane == 0 && wave < RP_WAVES)
-#pragma unroll
-        for (int i = 0; i < 10; ++i) smem[i * RP_WAVES + wave] = acc[i];
-    __syncthreads();
+    // the workgroup sum of wave_ops.h in its two halves: only the accumulating waves store, and thread 0 alone combines
+    wg_sum_publish<RP_WAVES>(acc, smem, threadIdx.x < RP_THREADS);
     if (threadIdx.x != 0) return;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) acc[i] = (smem[i * 4 + 0] + smem[i * 4 + 1]) + (smem[i * 4 + 2] + smem[i * 4 + 3]);
-    static_assert(RP_WAVES == 4, "the reduction above adds four waves");
+    wg_sum_combine<WG_SUM_PAIRS, RP_WAVES>(acc, smem);
     const float cnt = (float)acc[9];
     float dR[9];  // row-major
     if (sym) {

@@ -41,6 +41,7 @@ constexpr int cdiv_c(int a, int b) { return (a + b - 1) / b; }
 //  ASM = true: v_max3_f32 as an asm statement.  The form of the one-wave-per-SIMD kernels: their accumulators are AGPRs, the
 //    operands reach the statement through compiler-issued v_accvgpr_read (hazards handled there), and the opaque statement
 //    keeps the scheduler from interleaving the read-outs, which with llvm.maximum costs 700 bytes of scratch per lane.
+// (sa_x6.hip's sx_max3 is the ASM = false body alone, not a copy of this template: its kernels have no use for the asm form)
 template <bool ASM>
 __device__ __forceinline__ float sb_max3(float a, float b, float c) {
     if constexpr (ASM) {

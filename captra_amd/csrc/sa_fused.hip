@@ -190,7 +190,7 @@ __device__ __forceinline__ void sa_layer(int cin, int cout, const float *__restr
             for (int r = 0; r < 16; ++r) {
                 float v = (acc[tm][r] > 0.f && col_ok) ? acc[tm][r] : 0.f;
                 v = row16_maxf(v);
-                v = fmaxf(v, dppf_rm<0x142, 0xA>(v));
+                v = fmaxf(v, dpp_keep<0x142, 0xA>(v));
                 const int row = rbase + (r & 3) + 8 * (r >> 2);
                 if ((lane & 31) == 16 && row < cout) red[row * SF_SLOTS + red_slot + wn] = v;
             }

@@ -80,13 +80,6 @@ __device__ __forceinline__ void sp_mid_unit(const f32x16 &acc, int t, int q, flo
 // maximum is the largest positive float, otherwise the result is negative and the ReLU makes it 0 -- what ReLU-then-max
 // gives), and ONE 64-lane ds_write_b32 per tile.  The two rows of 16 of each half-wave are combined by the final cross-wave
 // pass, which reads 2 x 4 slots per output row instead of 4.  51 VALU + 1 DS per tile.
-__device__ __forceinline__ int sp_imax(int a, int b) { return a > b ? a : b; }
-
-template <int CTRL, int BANK_MASK>
-__device__ __forceinline__ int sp_dpp(int old, int src) {
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, 0xF, BANK_MASK, false);
-}
-
 struct SpMaxState {
     int w[8];   // after stage A (lane bit 0)
     int u[2];   // after stages B, C (lane bits 1, 2)
@@ -99,7 +92,7 @@ __device__ __forceinline__ void sp_max_stage_a(const f32x16 &acc, SpMaxState &st
     for (int i = 0; i < 8; ++i) {
         const int x0 = __float_as_int(acc[2 * i]), x1 = __float_as_int(acc[2 * i + 1]);
         const int own = b0 ? x1 : x0, oth = b0 ? x0 : x1;
-        st.w[i] = sw_imax_dpp<0xB1>(own, oth);                            // quad_perm [1,0,3,2]: lane ^ 1
+        st.w[i] = imax_dpp<0xB1>(own, oth);                            // quad_perm [1,0,3,2]: lane ^ 1
     }
 }
 
@@ -110,15 +103,15 @@ __device__ __forceinline__ void sp_max_stage_bc(SpMaxState &st, int lane) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int own = b1 ? st.w[2 * j + 1] : st.w[2 * j], oth = b1 ? st.w[2 * j] : st.w[2 * j + 1];
-        v[j] = sw_imax_dpp<0x4E>(own, oth);                                // quad_perm [2,3,0,1]: lane ^ 2
+        v[j] = imax_dpp<0x4E>(own, oth);                                // quad_perm [2,3,0,1]: lane ^ 2
     }
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         const int own = b2 ? v[2 * m + 1] : v[2 * m], oth = b2 ? v[2 * m] : v[2 * m + 1];
         // lane ^ 4: banks 0, 2 (lanes 0-3, 8-11 of a row) read four lanes up, banks 1, 3 four lanes down
-        const int p = sp_dpp<0x104, 0x5>(own, oth);                      // row_shl:4 into banks 0, 2; the others keep `own`
-        const int q = sp_dpp<0x114, 0xA>(p, oth);                        // row_shr:4 into banks 1, 3
-        st.u[m] = sp_imax(own, q);
+        const int p = dpp_keep<0x104, 0xF, 0x5>(own, oth);                    // row_shl:4 into banks 0, 2; the others keep `own`
+        const int q = dpp_keep<0x114, 0xF, 0xA>(p, oth);                      // row_shr:4 into banks 1, 3
+        st.u[m] = imax(own, q);
     }
 }
 
@@ -129,7 +122,7 @@ __device__ __forceinline__ void sp_max_stage_d(const SpMaxState &st, int &zr) {
     const int lane = (int)(threadIdx.x & 63);
     const bool b3 = lane & 8;
     const int own = b3 ? st.u[1] : st.u[0], oth = b3 ? st.u[0] : st.u[1];
-    zr = sw_imax(zr, sw_imax_dpp<0x128>(own, oth));                        // row_ror:8: lane ^ 8 within the row
+    zr = imax(zr, imax_dpp<0x128>(own, oth));                        // row_ror:8: lane ^ 8 within the row
 }
 
 template <int COUT, bool LAST, int NPARTS, int NOUT, int NZ>

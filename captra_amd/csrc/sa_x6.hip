@@ -26,6 +26,7 @@ namespace {
 constexpr int sx_max(int a, int b) { return a > b ? a : b; }
 constexpr int sx_pad128(int c) { return (c + 127) / 128 * 128; }
 
+// (sa_bf16.hip's sb_max3<ASM> adds an asm form for its one-wave-per-SIMD kernels; here the compiler's form alone is used)
 __device__ __forceinline__ float sx_max3(float a, float b, float c) {
     return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
 }

@@ -22,6 +22,7 @@
 // partial (sum, sum of squares) per channel and chunk of 128 positions, of the fp32 accumulator values, tile-major
 // (B, T, C, 2) for captra_gn_finalize_tm; fixed summation order, no atomics.
 #include "common.h"
+#include "wave_ops.h"
 #include "bf16_dense.h"
 #include <atomic>
 
@@ -264,8 +265,7 @@ __global__ __launch_bounds__(NW * 64, 2) void tb_layer_kernel(TbParams p) {
                 mx[r] = -INFINITY;
 #pragma unroll
                 for (int tn = 0; tn < TB_TN; ++tn) mx[r] = pos0 + tn * 32 + col < p.L ? fmaxf(mx[r], acc[tm][tn][r]) : mx[r];
-#pragma unroll
-                for (int off = 16; off >= 1; off >>= 1) mx[r] = fmaxf(mx[r], __shfl_xor(mx[r], off, 64));
+                WAVE_BUTTERFLY(mx[r], 16, fmaxf);
             }
             if (col == 0) {
                 float *yp = reinterpret_cast<float *>(p.y) + (size_t)b * p.cout + 32 * t + 4 * h;

@@ -4,6 +4,7 @@
 //                                  pointnet_utils.py:280-294 (three_nn + weights + interpolate + cat)
 //   captra_group_norm_relu         blocks.py:70-71 (GroupNorm(C/2, C)) + ReLU of MLPConv1d
 #include "common.h"
+#include "wave_ops.h"
 
 #include <math.h>
 
@@ -300,15 +301,6 @@ __global__ __launch_bounds__(IC_THREADS) void interp_concat_kernel(int n, int s,
 constexpr int GN_THREADS = 256;
 constexpr int GN_MAXV = 16;  // float4 per thread: supports cpg*N <= 256*16*4 = 16384 values per group
 
-__device__ __forceinline__ float block_sum(float v, float *smem) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) smem[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (smem[0] + smem[1]) + (smem[2] + smem[3]);
-}
-
 __global__ __launch_bounds__(GN_THREADS) void group_norm_relu_kernel(int c, int n, int cpg, float eps, int relu,
                                                                      const float *__restrict__ x,
                                                                      const float *__restrict__ gamma,
@@ -329,7 +321,7 @@ __global__ __launch_bounds__(GN_THREADS) void group_norm_relu_kernel(int c, int 
         v[i] = e < nv ? x4[e] : make_float4(0.f, 0.f, 0.f, 0.f);
         sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    const float mean = block_sum(sum, smem) / (float)total;
+    const float mean = wg_sum<WG_SUM_PAIRS, 4>(sum, smem) / (float)total;
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < GN_MAXV; ++i) {
@@ -339,7 +331,7 @@ __global__ __launch_bounds__(GN_THREADS) void group_norm_relu_kernel(int c, int 
             sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
         }
     }
-    const float var = block_sum(sq, smem) / (float)total;
+    const float var = wg_sum<WG_SUM_PAIRS, 4>(sq, smem) / (float)total;
     const float rstd = 1.0f / sqrtf(var + eps);
     float4 *y4 = reinterpret_cast<float4 *>(y + base);
 #pragma unroll

@@ -10,27 +10,11 @@
 // Accumulators start from the bias and K ascends within one wave: the k-ascending fmaf chain of the oracle.
 #pragma once
 #include "common.h"
+#include "wave_ops.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float row16_maxf(float v) {
-    v = fmaxf(v, dppf<0xB1>(v));
-    v = fmaxf(v, dppf<0x4E>(v));
-    v = fmaxf(v, dppf<0x141>(v));
-    v = fmaxf(v, dppf<0x140>(v));
-    return v;
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dppf_rm(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xF, false));
-}
 
 constexpr int pad32c(int c) { return (c + 31) / 32 * 32; }
 constexpr int pad128c(int c) { return (c + 127) / 128 * 128; }
@@ -129,20 +113,7 @@ __device__ __forceinline__ void sw_mid_epilogue(const f32x16 &acc, int t, float 
 // ReLU-then-max) and one 32-lane ds_write_b32 finish the tile: ~55 instructions instead of ~112.  These kernels are bound
 // by the instructions a SIMD issues (MFMA issue + VALU do not overlap within it: the phase timers move when an
 // instruction count moves and not when a latency does), so that is ~5 % of an SA1 scale.
-template <int CTRL, int BANK_MASK>
-__device__ __forceinline__ int sw_dpp_sel(int old, int src) {
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, 0xF, BANK_MASK, false);
-}
-__device__ __forceinline__ int sw_imax(int a, int b) { return a > b ? a : b; }
-// max(own, oth of the partner lane) for a permutation in which EVERY lane has a source (quad_perm, row_ror): with
-// bound_ctrl and a dead `old` the compiler folds the DPP move into the max (one v_max_i32_dpp instead of
-// v_mov + v_mov_dpp + v_max)
-template <int CTRL>
-__device__ __forceinline__ int sw_imax_dpp(int own, int oth) {
-    const int o = __builtin_amdgcn_update_dpp(0, oth, CTRL, 0xF, 0xF, true);
-    return o > own ? o : own;
-}
-
+// (imax_dpp, imax and the banked dpp_keep of the lane ^ 4 stage: wave_ops.h)
 template <int COUT, int RED_STRIDE = 4>
 __device__ __forceinline__ void sw_last_epilogue_bfly(const f32x16 &acc, int t, float *red, int wave, int lane) {
     const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
@@ -151,23 +122,23 @@ __device__ __forceinline__ void sw_last_epilogue_bfly(const f32x16 &acc, int t, 
     for (int i = 0; i < 8; ++i) {
         const int x0 = __float_as_int(acc[2 * i]), x1 = __float_as_int(acc[2 * i + 1]);
         const int own = b0 ? x1 : x0, oth = b0 ? x0 : x1;
-        w[i] = sw_imax_dpp<0xB1>(own, oth);                             // quad_perm [1,0,3,2]: lane ^ 1
+        w[i] = imax_dpp<0xB1>(own, oth);                             // quad_perm [1,0,3,2]: lane ^ 1
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int own = b1 ? w[2 * j + 1] : w[2 * j], oth = b1 ? w[2 * j] : w[2 * j + 1];
-        v[j] = sw_imax_dpp<0x4E>(own, oth);                             // quad_perm [2,3,0,1]: lane ^ 2
+        v[j] = imax_dpp<0x4E>(own, oth);                             // quad_perm [2,3,0,1]: lane ^ 2
     }
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         const int own = b2 ? v[2 * m + 1] : v[2 * m], oth = b2 ? v[2 * m] : v[2 * m + 1];
-        const int p = sw_dpp_sel<0x104, 0x5>(own, oth);                  // lane ^ 4: row_shl:4 into banks 0, 2 ...
-        const int q = sw_dpp_sel<0x114, 0xA>(p, oth);                    // ... row_shr:4 into banks 1, 3
-        u[m] = sw_imax(own, q);
+        const int p = dpp_keep<0x104, 0xF, 0x5>(own, oth);                  // lane ^ 4: row_shl:4 into banks 0, 2 ...
+        const int q = dpp_keep<0x114, 0xF, 0xA>(p, oth);                    // ... row_shr:4 into banks 1, 3
+        u[m] = imax(own, q);
     }
     const int own = b3 ? u[1] : u[0], oth = b3 ? u[0] : u[1];
-    int z = sw_imax_dpp<0x128>(own, oth);                                // row_ror:8: lane ^ 8 within the row of 16
-    z = sw_imax(z, __builtin_amdgcn_ds_swizzle(z, 0x401F));              // lane ^ 16: the other row of the half-wave
+    int z = imax_dpp<0x128>(own, oth);                                // row_ror:8: lane ^ 8 within the row of 16
+    z = imax(z, __builtin_amdgcn_ds_swizzle(z, 0x401F));              // lane ^ 16: the other row of the half-wave
     z = z > 0 ? z : 0;                                                   // ReLU on the bit pattern
     // lane l (l & 16 == 0) holds accumulator register r = l & 15 = output row 32 t + 8 (r >> 2) + (r & 3) + 4 (l >> 5)
     const int r = lane & 15;
@@ -186,27 +157,27 @@ __device__ __forceinline__ void sw_bfly_accumulate(const f32x16 &acc, int &zrun,
     for (int i = 0; i < 8; ++i) {
         const int x0 = __float_as_int(acc[2 * i]), x1 = __float_as_int(acc[2 * i + 1]);
         const int own = b0 ? x1 : x0, oth = b0 ? x0 : x1;
-        w[i] = sw_imax_dpp<0xB1>(own, oth);
+        w[i] = imax_dpp<0xB1>(own, oth);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int own = b1 ? w[2 * j + 1] : w[2 * j], oth = b1 ? w[2 * j] : w[2 * j + 1];
-        v[j] = sw_imax_dpp<0x4E>(own, oth);
+        v[j] = imax_dpp<0x4E>(own, oth);
     }
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         const int own = b2 ? v[2 * m + 1] : v[2 * m], oth = b2 ? v[2 * m] : v[2 * m + 1];
-        const int p = sw_dpp_sel<0x104, 0x5>(own, oth);
-        const int q = sw_dpp_sel<0x114, 0xA>(p, oth);
-        u[m] = sw_imax(own, q);
+        const int p = dpp_keep<0x104, 0xF, 0x5>(own, oth);
+        const int q = dpp_keep<0x114, 0xF, 0xA>(p, oth);
+        u[m] = imax(own, q);
     }
     const int own = b3 ? u[1] : u[0], oth = b3 ? u[0] : u[1];
-    zrun = sw_imax(zrun, sw_imax_dpp<0x128>(own, oth));
+    zrun = imax(zrun, imax_dpp<0x128>(own, oth));
 }
 // the finished maximum of output tile t's rows: valid in the lanes with (lane & 16) == 0, lane l = row
 // 32 t + 8 ((l & 15) >> 2) + (l & 3) + 4 (l >> 5)
 __device__ __forceinline__ float sw_bfly_finish(int zrun) {
-    return __int_as_float(sw_imax(zrun, __builtin_amdgcn_ds_swizzle(zrun, 0x401F)));     // lane ^ 16
+    return __int_as_float(imax(zrun, __builtin_amdgcn_ds_swizzle(zrun, 0x401F)));     // lane ^ 16
 }
 
 

@@ -59,6 +59,21 @@ def test_launch_plumbing_lives_in_common_h():
     assert not others, others
 
 
+def test_cross_lane_primitives_live_in_wave_ops_h():
+    """DPP moves, the xor-butterfly accumulation and the workgroup sum are csrc/wave_ops.h's: no kernel family carries a copy."""
+    csrc = ROOT / "captra_amd" / "csrc"
+    files = [p for p in sorted(csrc.iterdir()) if p.suffix in (".hip", ".h", ".cpp")]
+    assert (csrc / "wave_ops.h") in files
+    texts = {p.name: p.read_text() for p in files}
+    for word in ("__builtin_amdgcn_update_dpp", "+= __shfl_xor("):
+        holders = [name for name, text in texts.items() if word in text and name != "wave_ops.h"]
+        assert not holders, (word, holders)
+    assert "__builtin_amdgcn_update_dpp" in texts["wave_ops.h"]
+    removed = ("fp_dpp_max", "dpp_f<", "sp_dpp<", "sw_dpp_sel<", "block_reduce_sum", "rs_block_sum")
+    bad = [(name, word) for name, text in texts.items() for word in removed if word in text]
+    assert not bad, bad
+
+
 def test_pointnet2_cuda_module_surface():
     """Same ten callables as the reference's pybind module (pointnet2_api.cpp:10-25)."""
     import captra_amd
