@@ -139,12 +139,26 @@ __device__ __forceinline__ float dist2_unfused(float ax, float ay, float az, flo
 // activation codes of the shared-MLP entry points (include/captra_hip.h: CAPTRA_ACT_*)
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID_M05 = 2 };
 
-// ReLU on the bit pattern: negative floats (and -0) are negative integers, so one v_max_i32 does it; written on floats the
-// compiler emits a canonicalising v_max_f32 x, x, x in front of the v_max_f32 x, 0 (IEEE mode).  NaNs with the sign bit
-// clear pass through, as in the reference's relu.
+// ReLU as the reference's F.relu: a NaN of either sign and any payload stays that NaN (the fp32 MFMA itself generates the sign-SET
+// 0xFFC00000 from Inf - Inf, so a max on the bit pattern as a signed integer, one v_max_i32, turns exactly the NaNs a layer makes
+// into 0).  A compare and a select on the untouched bits: written as fmaxf(v, 0) the compiler emits a canonicalising
+// v_max_f32 x, x, x in front of a v_max_f32 x, 0 that returns the 0 for a quiet NaN (IEEE mode).  -0 and negatives give +0.
+// (The name is from the integer form it replaces; it no longer works on the bit pattern.  Every caller takes the new form and its
+// second instruction: the exact-fp32 dense kernels, the generic SA kernel, GroupNorm, and through apply_act the f32x6 and bf16 kernels'
+// epilogues (dense_x6, sa_x6, chain_x6, bf16_*), whose finite results are unchanged and whose NaN propagation is not tested.)
 __device__ __forceinline__ float relu_bits(float v) {
-    const int x = __float_as_int(v);
-    return __int_as_float(x > 0 ? x : 0);
+    return v <= 0.f ? 0.f : v;
+}
+// ReLU in front of a max pool, as a bit pattern: 0 for -0 and negatives, the value's own bits for a positive number, and a NaN
+// with its sign cleared.  The results are non-negative signed integers ordered as torch.max orders them (a NaN above +Inf), so
+// the pool behind it is an integer max (imax / imax_dpp, wave_ops.h) and hands a NaN on.
+__device__ __forceinline__ int relu_pool_bits(float v) {
+    return v <= 0.f ? 0 : (__float_as_int(v) & 0x7FFFFFFF);
+}
+// max of two floats that hands a NaN of either operand on (torch.max); fmaxf returns the other operand
+__device__ __forceinline__ float max_nan(float a, float b) {
+    const float m = a <= b ? b : a;          // a NaN a: a
+    return b != b ? b : m;
 }
 __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == ACT_RELU) return relu_bits(v);

@@ -271,7 +271,9 @@ __global__ __launch_bounds__(256) void otf_finish_kernel(int cap, int stride, in
     const double x0 = (q[0] - t[0]) / s, x1 = (q[1] - t[1]) / s, x2 = (q[2] - t[2]) / s;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        points_cn[((size_t)b * 3 + a) * n + i] = (float)q[a] - mean[b * 3 + a];
+        // (a NaN leaves with its sign clear, as from captra_canonicalize: include/captra_hip.h, "NaN / Inf contract")
+        const float pc = (float)q[a] - mean[b * 3 + a];
+        points_cn[((size_t)b * 3 + a) * n + i] = pc != pc ? __int_as_float(__float_as_int(pc) & 0x7FFFFFFF) : pc;
         nocs_cn[((size_t)b * 3 + a) * n + i] = o ? (float)((x0 * R[a] + x1 * R[3 + a]) + x2 * R[6 + a]) : 0.f;
     }
     labels[(size_t)b * n + i] = o ? 0 : 1;

@@ -259,13 +259,14 @@ __global__ __launch_bounds__(PW_THREADS) void pw_mlp_kernel(PwParams p) {
                 const bool col_ok = pos0 + (wn * TN + tn) * 32 + (lane & 31) < p.L;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    float v = acc[tm][tn][r];
-                    v = (v > 0.f && col_ok) ? v : 0.f;  // ReLU (the only activation followed by a max in the path)
-                    v = row16_maxf(v);
-                    v = fmaxf(v, __shfl_xor(v, 16, 64));
+                    // ReLU (the only activation followed by a max in the path) as a non-negative bit pattern, a NaN above +Inf:
+                    // the max is an integer max and hands a NaN on, as torch.max does
+                    int v = col_ok ? relu_pool_bits(acc[tm][tn][r]) : 0;
+                    v = row16_maxi(v);
+                    v = imax(v, __shfl_xor(v, 16, 64));
                     if ((lane & 31) == 0) {
                         const int rl = (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                        red[rl * NT + wn * TN + tn] = v;
+                        red[rl * NT + wn * TN + tn] = __int_as_float(v);
                     }
                 }
             }
@@ -277,9 +278,9 @@ __global__ __launch_bounds__(PW_THREADS) void pw_mlp_kernel(PwParams p) {
             const int row = co0 + rl;
             const long long centre = pos0 / p.k + g;
             if (row < p.cout && centre < p.m) {
-                float v = red[rl * NT + g * tiles_per_group];
-                for (int t = 1; t < tiles_per_group; ++t) v = fmaxf(v, red[rl * NT + g * tiles_per_group + t]);
-                p.y[((size_t)b * p.y_ctotal + p.co_off + row) * p.m + centre] = v;
+                int v = __float_as_int(red[rl * NT + g * tiles_per_group]);
+                for (int t = 1; t < tiles_per_group; ++t) v = imax(v, __float_as_int(red[rl * NT + g * tiles_per_group + t]));
+                p.y[((size_t)b * p.y_ctotal + p.co_off + row) * p.m + centre] = __int_as_float(v);
             }
         }
     }
@@ -697,7 +698,7 @@ __global__ __launch_bounds__(256) void pw_splitk_kernel(PwParams p) {
 // Dense layer + ReLU + max over groups of K consecutive positions (K in {32, 64, 128}; SA3's last layer over its 128 points,
 // reference pointnet_utils.py:336-343), direct-operand form: a workgroup = 4 waves x 32 positions x one 32-row output
 // tile, both operands prefetched 16 k-steps ahead (one accumulator chain per wave, so the sets are deep), ReLU and the
-// 32-lane max on the bit patterns (v_max_i32_dpp), the 4 waves' maxima combined through LDS.
+// 32-lane max on the bit patterns (v_max_i32_dpp; relu_pool_bits: a NaN of either sign wins), the 4 waves' maxima combined through LDS.
 __global__ __launch_bounds__(256) void pw_direct_max_kernel(PwParams p) {
     constexpr int KS = 16;
     __shared__ float red[32 * 4];
@@ -747,8 +748,7 @@ __global__ __launch_bounds__(256) void pw_direct_max_kernel(PwParams p) {
     int v[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int xbits = __float_as_int(acc[r]);
-        v[r] = (xbits > 0 && col_ok) ? xbits : 0;       // ReLU on the bit pattern; columns beyond L contribute 0
+        v[r] = col_ok ? relu_pool_bits(acc[r]) : 0;      // ReLU as a non-negative bit pattern (a NaN above +Inf); columns beyond L contribute 0
     }
 #define PM_STEP(CTRL) \
     _Pragma("unroll") for (int r = 0; r < 16; ++r) v[r] = imax_dpp<CTRL>(v[r], v[r]);     // (v >= 0: 0 is the identity)
@@ -769,9 +769,9 @@ __global__ __launch_bounds__(256) void pw_direct_max_kernel(PwParams p) {
         const int row = e / groups, gi = e % groups;
         const long long g = blk0 / p.k + gi;
         if (g < p.m && co0 + row < p.cout) {
-            float mx = red[row * 4 + gi * tiles_per_group];
-            for (int t = 1; t < tiles_per_group; ++t) mx = fmaxf(mx, red[row * 4 + gi * tiles_per_group + t]);
-            p.y[((size_t)b * p.y_ctotal + p.co_off + co0 + row) * p.m + g] = mx;
+            int mx = __float_as_int(red[row * 4 + gi * tiles_per_group]);
+            for (int t = 1; t < tiles_per_group; ++t) mx = imax(mx, __float_as_int(red[row * 4 + gi * tiles_per_group + t]));
+            p.y[((size_t)b * p.y_ctotal + p.co_off + co0 + row) * p.m + g] = __int_as_float(mx);
         }
     }
 }

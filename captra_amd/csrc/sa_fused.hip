@@ -180,19 +180,18 @@ __device__ __forceinline__ void sa_layer(int cin, int cout, const float *__restr
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ro = (r & 3) + 8 * (r >> 2);
-                const float v = acc[tm][r] > 0.f ? acc[tm][r] : 0.f;
-                if (rbase + ro < cout) hp[(size_t)ro * SF_T] = v;
+                if (rbase + ro < cout) hp[(size_t)ro * SF_T] = relu_bits(acc[tm][r]);
             }
         } else {
             // max over the 32 positions of this MFMA tile: 4 DPP steps inside each row of 16 lanes, then
             // row_bcast15 folds row 0 into row 1 and row 2 into row 3 (no LDS permute); lanes 16 / 48 write
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                float v = (acc[tm][r] > 0.f && col_ok) ? acc[tm][r] : 0.f;
-                v = row16_maxf(v);
-                v = fmaxf(v, dpp_keep<0x142, 0xA>(v));
+                int v = col_ok ? relu_pool_bits(acc[tm][r]) : 0;        // non-negative bit patterns, a NaN above +Inf: an integer max
+                v = row16_maxi(v);
+                v = imax(v, dpp_keep<0x142, 0xA>(v));
                 const int row = rbase + (r & 3) + 8 * (r >> 2);
-                if ((lane & 31) == 16 && row < cout) red[row * SF_SLOTS + red_slot + wn] = v;
+                if ((lane & 31) == 16 && row < cout) red[row * SF_SLOTS + red_slot + wn] = __int_as_float(v);
             }
         }
     }
@@ -297,9 +296,9 @@ __global__ __launch_bounds__(256 * WN) __attribute__((amdgpu_waves_per_eu(4, 8))
         const int row = e / groups, gi = e % groups;
         const long long centre = pos0 / p.k + gi;
         if (centre < p.m) {
-            float v = red[row * SF_SLOTS + gi * tiles_per_group];
-            for (int t = 1; t < tiles_per_group; ++t) v = fmaxf(v, red[row * SF_SLOTS + gi * tiles_per_group + t]);
-            p.out[((size_t)b * p.out_ctotal + p.co_off + row) * p.m + centre] = v;
+            int v = __float_as_int(red[row * SF_SLOTS + gi * tiles_per_group]);
+            for (int t = 1; t < tiles_per_group; ++t) v = imax(v, __float_as_int(red[row * SF_SLOTS + gi * tiles_per_group + t]));
+            p.out[((size_t)b * p.out_ctotal + p.co_off + row) * p.m + centre] = __int_as_float(v);
         }
     }
 }
@@ -534,9 +533,10 @@ void sa_wave_kernel(SwParams p) {
         const int row = e / groups, gi = e % groups;
         const long long centre = pos0 / p.k + gi;
         if (centre < p.m) {
-            float v = red[row * 4 + gi * tiles_per_group];
-            for (int t = 1; t < tiles_per_group; ++t) v = fmaxf(v, red[row * 4 + gi * tiles_per_group + t]);
-            p.out[((size_t)b * p.out_ctotal + p.co_off + row) * p.m + centre] = v;
+            // (the tiles' maxima are non-negative bit patterns, a sign-clear NaN above +Inf: fmaxf would drop it)
+            int v = __float_as_int(red[row * 4 + gi * tiles_per_group]);
+            for (int t = 1; t < tiles_per_group; ++t) v = imax(v, __float_as_int(red[row * 4 + gi * tiles_per_group + t]));
+            p.out[((size_t)b * p.out_ctotal + p.co_off + row) * p.m + centre] = __int_as_float(v);
         }
     }
 }

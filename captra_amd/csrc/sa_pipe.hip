@@ -55,7 +55,7 @@ struct SpParams {
 // Part c of NPARTS takes the units with u * NPARTS / UNITS == c, so the work spreads evenly over a pass's k-step sets.
 template <int NOUT>
 __device__ __forceinline__ void sp_mid_unit(const f32x16 &acc, int t, int q, float (&hout)[NOUT]) {
-    unsigned a[4];          // ReLU on the bit pattern: one v_max_i32 (the float form is canonicalise + max)
+    unsigned a[4];          // ReLU on the bit pattern: one v_max_i32 (the float form is canonicalise + max); sign-clear NaNs only (wave_mlp.h)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int x = __float_as_int(acc[4 * q + i]);

@@ -43,7 +43,10 @@ __global__ __launch_bounds__(256) void canonicalize_kernel(int p, int n, const f
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float acc = (R[0 * 3 + a] * v[0] + R[1 * 3 + a] * v[1]) + R[2 * 3 + a] * v[2];
-        const float o = acc / s;
+        // where external data enters the networks a NaN leaves with its sign CLEAR: the register-resident wave kernels hand only
+        // those on (include/captra_hip.h, "NaN / Inf contract"); every other value keeps its bits
+        const float q0 = acc / s;
+        const float o = q0 != q0 ? __int_as_float(__float_as_int(q0) & 0x7FFFFFFF) : q0;
         if (out_cn) out_cn[((size_t)q * 3 + a) * n + i] = o;
         if (out_n3) out_n3[((size_t)q * n + i) * 3 + a] = o;
         if (out_planes) out_planes[((size_t)q * 3 + a) * npad + pa] = o;
@@ -346,8 +349,8 @@ __global__ __launch_bounds__(GN_THREADS) void group_norm_relu_kernel(int c, int 
             o.z = (v[i].z - mean) * ga + be;
             o.w = (v[i].w - mean) * ga + be;
             if (relu) {
-                o.x = o.x > 0.f ? o.x : 0.f; o.y = o.y > 0.f ? o.y : 0.f;
-                o.z = o.z > 0.f ? o.z : 0.f; o.w = o.w > 0.f ? o.w : 0.f;
+                // (F.relu: a group that holds one non-finite value is all NaN in nn.GroupNorm, and stays so)
+                o.x = relu_bits(o.x); o.y = relu_bits(o.y); o.z = relu_bits(o.z); o.w = relu_bits(o.w);
             }
             y4[e] = o;
         }
@@ -419,7 +422,8 @@ __global__ __launch_bounds__(256) void copy_multi_kernel(CopyMulti m) {
     }
 }
 
-// out[r] = max over the l floats of row r (group_all pooling of a (B,C,N) tensor: pointnet_utils.py:342 torch.max(new_points, 2)):
+// out[r] = max over the l floats of row r (group_all pooling of a (B,C,N) tensor: pointnet_utils.py:342 torch.max(new_points, 2);
+// a NaN in the row is the row's maximum, as there):
 // 32 lanes per row, 16-byte loads when the rows allow it
 __global__ __launch_bounds__(256) void row_max_kernel(long long rows, int l, const float *__restrict__ x, float *__restrict__ out) {
     const long long r = (long long)blockIdx.x * 8 + (threadIdx.x >> 5);
@@ -430,14 +434,14 @@ __global__ __launch_bounds__(256) void row_max_kernel(long long rows, int l, con
         if ((l & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
             for (int i = lane * 4; i < l; i += 128) {
                 const float4 v = *reinterpret_cast<const float4 *>(row + i);
-                m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+                m = max_nan(max_nan(m, max_nan(v.x, v.y)), max_nan(v.z, v.w));
             }
         } else {
-            for (int i = lane; i < l; i += 32) m = fmaxf(m, row[i]);
+            for (int i = lane; i < l; i += 32) m = max_nan(m, row[i]);
         }
     }
 #pragma unroll
-    for (int off = 16; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 32));
+    for (int off = 16; off >= 1; off >>= 1) m = max_nan(m, __shfl_xor(m, off, 32));
     if (r < rows && lane == 0) out[r] = m;
 }
 

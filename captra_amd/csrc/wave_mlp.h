@@ -85,7 +85,10 @@ __device__ __forceinline__ void sw_mid_epilogue(const f32x16 &acc, int t, float 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         // ReLU on the bit pattern (one v_max_i32: negative floats and -0 are negative integers; the float form costs a
-        // canonicalising v_max_f32 x, x, x in front of every v_max_f32 x, 0 -- 88 instructions per SA1 tile)
+        // canonicalising v_max_f32 x, x, x in front of every v_max_f32 x, 0 -- 88 instructions per SA1 tile).  A sign-clear NaN
+        // is the largest integer and passes, as in F.relu; a sign-SET one (an input, or the 0xFFC00000 the MFMA generates from
+        // Inf - Inf) becomes 0: the documented exception of include/captra_hip.h ("NaN / Inf contract"), here and in the
+        // integer pools below, which such a NaN loses.  relu_bits (common.h) is the form without the exception, at two instructions.
         unsigned a[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {

@@ -69,14 +69,15 @@ static __device__ __forceinline__ unsigned wave_min_u32(unsigned v) { return wav
 static __device__ __forceinline__ unsigned row_max_u32_fold(unsigned v) { return row16_reduce<true>(v, UMaxOp()); }
 static __device__ __forceinline__ unsigned wave_max_u32_fold(unsigned v) { return wave64_reduce_u32<true>(v, UMaxOp()); }
 static __device__ __forceinline__ unsigned wave_min_u32_fold(unsigned v) { return ~wave_max_u32_fold(~v); }
-static __device__ __forceinline__ float row16_maxf(float v) { return row16_reduce<false>(v, [](float a, float b) { return fmaxf(a, b); }); }
+static __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
+// the max pools' row step, on the non-negative bit patterns of relu_pool_bits (common.h: a NaN above +Inf; fmaxf would drop it)
+static __device__ __forceinline__ int row16_maxi(int v) { return row16_reduce<false>(v, [](int a, int b) { return imax(a, b); }); }
 // sum over each half-wave (32 lanes): valid in lanes 16..31 (lower half) and 48..63 (upper half)
 static __device__ __forceinline__ float half_wave_sum(float v) {
     v = row16_reduce<true>(v, [](float a, float b) { return a + b; });
     return v + dpp_zero<0x142, 0xA>(v);            // row_bcast15: rows 1 and 3 add rows 0 and 2
 }
 
-static __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 // max(own, oth of the partner lane) for a permutation in which EVERY lane has a source (quad_perm, row_ror): one v_max_i32_dpp
 template <int CTRL>
 static __device__ __forceinline__ int imax_dpp(int own, int oth) {

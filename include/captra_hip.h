@@ -144,6 +144,7 @@ int captra_three_interpolate_grad_ws(int b, int c, int n, int m, const float *gr
  * mean (B,3); rot (B*P,3,3); trans (B*P,3); scale (B*P); cloud q = b*P + p reads pts[b].
  * Writes out_cn (B*P,3,N) channel-major (network input) and out_n3 (B*P,N,3) point-major
  * (what FPS / ball query / three_nn consume).  Either output may be NULL. */
+/* NaN / Inf: handed on; every NaN written is sign-clear (contract below, before captra_pointwise_mlp). */
 int captra_canonicalize(int b, int p, int n, const float *pts, const float *mean, const float *rot,
                         const float *trans, const float *scale, float *out_cn, float *out_n3,
                         captra_stream_t stream);
@@ -181,12 +182,30 @@ int captra_pack_weights(int cin, int cout, const float *wt, const float *bias, f
                         float *bias_packed, captra_stream_t stream);
 int captra_pack_weights_frag(int cin, int cout, float *wt_packed, captra_stream_t stream);
 
+/* NaN / Inf CONTRACT of the exact-fp32 mode (tests/test_f32_edges_gpu.py, judge tests/f32_judge.py).  The reference's: an output
+ * that network/models makes NaN / +Inf / -Inf is NaN / +Inf / -Inf here, whatever the NaN's sign and payload, and an output that
+ * does not depend on a non-finite input keeps its bits.  ReLU is F.relu (a NaN stays a NaN), the max over the K neighbours and
+ * captra_row_max are torch.max (a NaN among the values is the maximum), a (cloud, group) of GroupNorm that holds one non-finite
+ * value is all NaN, and the zero rows that pad a layer to its tile never meet an Inf.  Finite inputs give the bits they always gave.
+ *   On gfx950 the fp32 MFMA hands an input NaN on with its sign and payload (quieted), under weights of either sign, and the NaN
+ *   it GENERATES (Inf - Inf, 0 * Inf in one dot product) is 0xFFC00000: sign-SET (measured).
+ * EXCEPTION, the register-resident wave kernels -- captra_sa_scale_fused / _pre / _pre_pm / captra_sa_scales_multi at the backbone's
+ * channel shapes, captra_mlp_chain3 and captra_coord_tail at theirs (csrc/wave_mlp.h, csrc/sa_pipe.hip): their inner ReLUs and their
+ * max over K stay ONE integer instruction on the bit pattern (these kernels are bound by instruction issue; a second instruction per
+ * accumulator was built and measured at 2.3 % of a step against a run-to-run spread of 0.3 %: DESIGN.md section 5).  They REQUIRE SIGN-CLEAR NaNs: a sign-clear NaN (0x7FC00000, 0x7F800001, ...) behaves as
+ * in the reference at every ReLU and pool; a sign-SET NaN -- an input, or the one the MFMA generates inside the kernel -- is a
+ * negative integer: 0 behind the next inner ReLU, the loser of the pool (the output is then finite where the reference's is NaN).
+ * The last activation of captra_mlp_chain3 / captra_coord_tail is the reference's.  captra_canonicalize and the crop
+ * (captra_otf_finish), where external data enters the networks, write every NaN sign-clear.  The f32x6 and bf16 modes are held to
+ * containment only (tests/test_x6_edges_gpu.py, tests/test_bf16_edges_gpu.py); their propagation is untested. */
+
 /* One shared-MLP layer, y = act(W x + bias), as an exact-fp32 MFMA GEMM over positions
  * (Conv2d/Conv1d 1x1 + folded BatchNorm + ReLU, pointnet_utils.py:242-245, 296-298).
  *   x (B, cin, L) f32, wt / bias PACKED (see above) -> y (B, cout, L).
  *   act: 0 none, 1 ReLU, 2 sigmoid(x) - 0.5 (networks.py:46).
  * Arithmetic contract: acc = bias; for k in 0..cin-1: acc = fmaf(W[co][k], x[k][l], acc)
  * (what v_mfma_f32_32x32x2_f32 computes), then the activation. */
+/* NaN / Inf: the reference's, for a NaN of either sign and in every form of the layer (direct, LDS-staged, paired columns, split-k). */
 int captra_pointwise_mlp(int b, int cin, int cout, long long l, const float *x, const float *wt,
                          const float *bias, int act, float *y, captra_stream_t stream);
 int captra_pointwise_mlp_ex(int b, int cin, int cout, long long l, const float *x, const float *wt,
@@ -196,6 +215,7 @@ int captra_pointwise_mlp_ex(int b, int cin, int cout, long long l, const float *
  * For a layer on [x; repeat(v)] with one vector v per cloud (pointnet_utils.py:265-270) after the caller has formed
  * bias_bc[b] = W2 v[b] + bias (captra_pointwise_mlp with l = 1): a third of the products, but not the k-ascending chain over the
  * concat -- the f32x6 mode uses it, the exact mode keeps captra_pointwise_mlp2.  -2: shape outside the direct kernels. */
+/* NaN / Inf: the reference's, for a NaN of either sign (contract above). */
 int captra_pointwise_mlp_cb(int b, int cin, int cout, long long l, const float *x, const float *wt,
                             const float *bias_bc, int act, float *y, captra_stream_t stream);
 
@@ -205,6 +225,7 @@ int captra_pointwise_mlp_cb(int b, int cin, int cout, long long l, const float *
  *                  = xyz_cn[b][ci-cfeat][idx] - new_xyz[b][m]   for ci >= cfeat   (3 channels)
  * feat (B,cfeat,N) or NULL when cfeat == 0; xyz_cn (B,3,N); new_xyz (B,M,3); idx (B,M,K).
  * y (B,cout,M,K) = relu(W x + bias), same arithmetic contract as captra_pointwise_mlp. */
+/* NaN / Inf: the reference's; dependence follows idx (a point named in no slot, or in padded slots only, reaches exactly those centres). */
 int captra_sa_group_mlp(int b, int n, int m, int k, int cfeat, int cout, const float *feat,
                         const float *xyz_cn, const float *new_xyz, const int *idx, const float *wt,
                         const float *bias, float *y, captra_stream_t stream);
@@ -213,6 +234,7 @@ int captra_sa_group_mlp(int b, int n, int m, int k, int cfeat, int cout, const f
  * epilogue (pointnet_utils.py:245-246): x (B,cin,M,K) -> y[b][co_off+co][m] =
  * max_k relu(W x + bias), y being (B, y_ctotal, M) so that the scales of one SA level write
  * straight into the concatenated tensor (pointnet_utils.py:249). */
+/* NaN / Inf: the reference's: a NaN of either sign among the K values is the maximum. */
 int captra_mlp_max(int b, int cin, int cout, int m, int k, const float *x, const float *wt,
                    const float *bias, float *y, int y_ctotal, int co_off, captra_stream_t stream);
 
@@ -222,6 +244,8 @@ int captra_mlp_max(int b, int cin, int cout, int m, int k, const float *x, const
  * Shapes as captra_sa_group_mlp / captra_mlp_max; w_i / b_i PACKED (see captra_pack_weights);
  * k in {32, 64, 128}, c_i <= 256.  out (B,out_ctotal,M) receives channels [co_off, co_off + c3).
  * Bit-identical to captra_sa_group_mlp -> captra_pointwise_mlp -> captra_mlp_max. */
+/* NaN / Inf: the generic kernel (shapes outside the backbone's) the reference's; the register-resident kernels require sign-clear
+ * NaNs (EXCEPTION above). */
 int captra_sa_scale_fused(int b, int n, int m, int k, int cfeat, int c1, int c2, int c3, const float *feat,
                           const float *xyz_cn, const float *new_xyz, const int *idx, const float *w1,
                           const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
@@ -242,6 +266,8 @@ int captra_sa_scale_fused_ex(int b, int n, int m, int k, int cfeat, int c1, int 
  * captra_gn_finalize reduces the partials (fixed order, double precision) to ab (B,c,2): a = gamma*rstd, b = beta - mean*a,
  * mean / biased variance over the group's channels_per_group channels x n positions (torch.nn.GroupNorm semantics).
  * Same convolution bits as captra_pointwise_mlp; the normalisation differs from a two-pass GroupNorm by rounding only. */
+/* NaN / Inf: the reference's, relu(a*x + b) on load included; a statistics tile that holds a non-finite output is non-finite, the other
+ * tiles keep their bits; captra_gn_finalize makes the whole (cloud, group) NaN from one such tile, as nn.GroupNorm does. */
 int captra_pointwise_mlp_gn(int b, int cin, int cout, long long l, const float *x, const float *wt_packed,
                             const float *bias_packed, const float *ab_in, int act, float *y, float *stats_out,
                             int stats_t, captra_stream_t stream);
@@ -559,6 +585,7 @@ int captra_sa1_stream_bf16(int b, int n, int m, const float *xyz_n3, const float
  * The kernel gathers v1[:, idx] as the accumulator start and continues the chain with the xyz rows of w1 (same packed
  * buffer), then layers 2, 3 and the max as captra_sa_scale_fused.  Bit-identical to captra_sa_scale_fused at ~60 % of its
  * flops for the SA2 scales.  Instantiated for (cfeat,c1,c2,c3) = (320,128,128,256), (320,128,196,256); -2 otherwise. */
+/* NaN / Inf: requires sign-clear NaNs (EXCEPTION above). */
 int captra_sa_scale_pre(int b, int n, int m, int k, int cfeat, int c1, int c2, int c3, const float *v1,
                         const float *xyz_cn, const float *new_xyz, const int *idx, const float *w1, const float *w2,
                         const float *b2, const float *w3, const float *b3, float *out, int out_ctotal, int co_off,
@@ -569,6 +596,7 @@ int captra_sa_scale_pre(int b, int n, int m, int k, int cfeat, int c1, int c2, i
  * (B,N,c1) result of captra_pointwise_mlp_pm.  Same k-ascending chains: bit-identical to captra_sa_scale_pre /
  * captra_sa_scale_fused.  w1, w2, w3 PACKED (both images, see PACKED WEIGHTS): the kernel streams the fragment images of
  * layers 2 / 3.  -2 when the shape is not instantiated or m*k is not a multiple of 128 (take captra_sa_scale_pre). */
+/* NaN / Inf: requires sign-clear NaNs (EXCEPTION above). */
 int captra_sa_scale_pre_pm(int b, int n, int m, int k, int cfeat, int c1, int c2, int c3, const float *v1pm,
                            const float *xyz_cn, const float *new_xyz, const int *idx, const float *w1, const float *w2,
                            const float *b2, const float *w3, const float *b3, float *out, int out_ctotal, int co_off,
@@ -584,6 +612,7 @@ int captra_sa_scale_pre_pm_ex(int b, int n, int m, int k, int cfeat, int c1, int
  * x2 (B,cin - csplit,L), or (B,cin - csplit) with x2_bcast = 1 (one vector per cloud, read for every position).  Rows are consumed
  * in the concat's order: bit-identical to captra_pointwise_mlp on the concatenated tensor.  -2: outside the instantiated shapes
  * (cout <= 64) or the tensors lie more than 2^30 bytes apart -- the caller concatenates. */
+/* NaN / Inf: the reference's, for a poison in either source (one in a per-cloud x2 reaches every position of its cloud). */
 int captra_pointwise_mlp2(int b, int cin, int csplit, int cout, long long l, const float *x, const float *x2, int x2_bcast,
                           const float *wt_packed, const float *bias_packed, int act, float *y, captra_stream_t stream);
 int captra_pointwise_mlp2_ex(int b, int cin, int csplit, int cout, long long l, const float *x, const float *x2, int x2_bcast,
@@ -591,6 +620,7 @@ int captra_pointwise_mlp2_ex(int b, int cin, int csplit, int cout, long long l, 
         captra_stream_t stream);   /* the same with per-call options */
 /* captra_pointwise_mlp with a POINT-major result y (B,l,cout) (cout % 4 == 0, y 16-byte aligned; -2 otherwise or when the
  * layer is outside the direct-operand kernel's 32-bit offset range). */
+/* NaN / Inf: the reference's, for a NaN of either sign (contract above). */
 int captra_pointwise_mlp_pm(int b, int cin, int cout, long long l, const float *x, const float *wt_packed,
                             const float *bias_packed, int act, float *y, captra_stream_t stream);
 int captra_pointwise_mlp_pm_ex(int b, int cin, int cout, long long l, const float *x, const float *wt_packed,
@@ -602,6 +632,8 @@ int captra_pointwise_mlp_pm_ex(int b, int cin, int cout, long long l, const floa
  * (pointnet_utils.py:296-298, backbones.py:66-68) without the two intermediate (B,128,l) tensors.  Instantiated
  * for (c0,c1,c2,c3) = (134,128,128,128) and (131,128,128,128); returns -2 for any other shape (run the layers
  * with captra_pointwise_mlp then).  Bit-identical to three captra_pointwise_mlp calls. */
+/* NaN / Inf: the one-launch chain requires sign-clear NaNs at its two inner ReLUs (EXCEPTION above), act3 is the reference's; the
+ * layer-by-layer route is the reference's throughout. */
 int captra_mlp_chain3(int b, int c0, int c1, int c2, int c3, long long l, const float *x, const float *w1,
                       const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, int act3,
                       float *y, captra_stream_t stream);
@@ -612,6 +644,7 @@ int captra_mlp_chain3(int b, int c0, int c1, int c2, int c3, long long l, const 
  * sigmoid - 0.5).  w / bias: HOST arrays of the six layers' packed device pointers in that order (fp1a, fp1b, conv1, seg,
  * nocs hidden, nocs out); hidden widths 128.  Instantiated for c0 = 134 and (seg_dim, nocs_dim) in {(2,3), (4,12), (3,9), (2,6)};
  * -2 otherwise.  Every output equals the corresponding chain of captra_pointwise_mlp calls bit for bit (sigmoid: same expf). */
+/* NaN / Inf: requires sign-clear NaNs at its inner ReLUs (EXCEPTION above); sigmoid(+-Inf) - 0.5 = +-0.5, a NaN stays a NaN. */
 int captra_coord_tail(int b, int c0, int seg_dim, int nocs_dim, long long l, const float *x, const float *const *w,
                       const float *const *bias, int nocs_act, float *seg, float *nocs, captra_stream_t stream);
 
@@ -624,6 +657,8 @@ int captra_coord_tail(int b, int c0, int seg_dim, int nocs_dim, long long l, con
  *   captra_fp_interpolate_concat: both, with caller-provided scratch idx (B,N,3) / weight (B,N,3). */
 int captra_three_nn_weights(int b, int n, int s, const float *unknown, const float *known, int *idx,
                             float *weight, captra_stream_t stream);
+/* NaN / Inf: the reference's; a non-finite feat_known value reaches every point that has it among its three neighbours (0 * Inf = NaN
+ * under a zero weight, as in the reference), one in skip only itself. */
 int captra_interp_concat(int b, int n, int s, int c1, int c2, const float *skip, const float *feat_known,
                          const int *idx, const float *weight, float *out, captra_stream_t stream);
 int captra_fp_interpolate_concat(int b, int n, int s, int c1, int c2, const float *unknown,
@@ -634,6 +669,7 @@ int captra_fp_interpolate_concat(int b, int n, int s, int c1, int c2, const floa
  * (nn.GroupNorm(C/2, C) + ReLU of the rotation heads, blocks.py:70-71, 148-165): one pass, the
  * group's values stay in registers between the statistics and the normalisation.
  * N % 4 == 0 and channels_per_group * N <= 16384. */
+/* NaN / Inf: the reference's: one non-finite value makes its whole (cloud, group) NaN, with and without the ReLU. */
 int captra_group_norm_relu(int b, int c, int n, int channels_per_group, float eps, int relu, const float *x,
                            const float *gamma, const float *beta, float *y, captra_stream_t stream);
 
@@ -779,7 +815,8 @@ int captra_seg_softmax_argmax(int b, int s, int n, const float *logits, float *s
 int captra_copy_multi(int njobs, const void *const *src, void *const *dst, const long long *bytes, captra_stream_t stream);
 
 /* out (rows) = max over each row of x (rows, l) fp32: the pooling of a group_all set abstraction (pointnet_utils.py:342,
- * torch.max(new_points, 2)[0]) on a (B,C,N) tensor, rows = B*C.  NaN handling as fmaxf (a NaN is ignored), unlike torch.max. */
+ * torch.max(new_points, 2)[0]) on a (B,C,N) tensor, rows = B*C.
+ * NaN / Inf: torch.max's: a NaN of either sign in the row is the row's maximum. */
 int captra_row_max(long long rows, int l, const float *x, float *out, captra_stream_t stream);
 
 /* The packed pose records of the per-frame exchange (no reference counterpart: the reference is one
@@ -848,6 +885,7 @@ typedef struct captra_sa_scale_job {
     float *out;
     int out_ctotal, co_off;
 } captra_sa_scale_job;
+/* NaN / Inf: as the jobs' own entry points (captra_sa_scale_fused / captra_sa_scale_pre_pm). */
 int captra_sa_scales_multi(int njobs, const captra_sa_scale_job *jobs, const captra_launch_opts *opts, captra_stream_t stream);
 
 /* Box IoUs of the evaluation tables (pose_utils/bbox_utils.py:11-61: pts_inside_box, iou_3d, nocs_iou_3d; the best of the candidate

@@ -252,7 +252,7 @@ EXPORT void oracle_canonicalize(int b, int p, int n, const float *pts, const flo
  * pointnet_utils.py:242-245 / 296-298; arithmetic contract of include/captra_hip.h:
  * acc = bias; acc = fmaf(W[co][k], x[k][l], acc) for k ascending; then the activation. */
 static inline float act_apply(float v, int act) {
-    if (act == 1) return v > 0.f ? v : 0.f;
+    if (act == 1) return v <= 0.f ? 0.f : v;        /* F.relu: a NaN of either sign stays a NaN */
     if (act == 2) return 1.0f / (1.0f + expf(-v)) - 0.5f;
     return v;
 }
@@ -302,7 +302,8 @@ EXPORT void oracle_max_over_k(int b, int c, int m, int k, const float *x, float 
             for (int mi = 0; mi < m; ++mi) {
                 const float *r = x + (((size_t)bi * c + ci) * m + mi) * k;
                 float best = r[0];
-                for (int j = 1; j < k; ++j) best = r[j] > best ? r[j] : best;
+                /* torch.max(..., -1): a NaN among the K wins, whatever its sign */
+                for (int j = 1; j < k; ++j) best = (r[j] > best || r[j] != r[j]) ? r[j] : best;
                 y[((size_t)bi * y_ctotal + co_off + ci) * m + mi] = best;
             }
 }
