@@ -134,7 +134,11 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void ball_query_kernel(int n, int m,
                 }
             const float ext = fmaxf(fmaxf(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]);
             float rp = 0.f;                                   // largest radius answered from the grid
-            if (ext > 0.f && ext < inf) {
+            // fminf / fmaxf drop NaNs: an axis on which EVERY coordinate is NaN keeps (lo, hi) = (+inf, -inf) while the other axes
+            // give a finite positive ext -- its cell count would come out of (int)(-inf).  A grid needs a box on every axis; with
+            // hi >= lo everywhere and ext < inf all six bounds are finite and every f below is finite and >= 0.
+            const bool boxed = hi[0] >= lo[0] && hi[1] >= lo[1] && hi[2] >= lo[2];
+            if (boxed && ext > 0.f && ext < inf) {
 #pragma unroll
                 for (int r = 0; r < NR; ++r)
                     if (prm.rad[r] > 0.f && prm.rad[r] <= 0.15f * ext && prm.ns[r] > 0) {
@@ -144,9 +148,14 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void ball_query_kernel(int n, int m,
             }
             any_pruned = rp > 0.f;
             if (any_pruned) {
-                // cell edge: a hair above rp, so that |x_p - x_c| < r (as the float test sees it) puts p within one cell of c
-                // along every axis whatever the roundings of the cell coordinates (margin 1e-4 against ~1e-6); enlarged
-                // until the grid has at most BQ_MAXCELLS cells
+                // cell edge: above rp by a margin that covers the roundings of the cell coordinates, so that a hit of the float test puts
+                // p within one cell of c along every axis.  The test d2 < r2 implies |x_p - x_c| < r (1 + 2u), u = 2^-24 (one rounding
+                // each in the difference, its square and r * r; the sum of non-negative squares only adds).  A cell coordinate is
+                // t^ = fl(fl(x - lo) * inv_c) = t (1 + th), |th| <= 2u + u^2, so it is off by up to 2.0001 u t -- 1e-6 cells in a grid of
+                // 16 cells, but 5e-4 in one of 4096 (a collinear cloud).  |t^_p - t^_c| <= r (1 + 2u) inv_c + 4.0002 u G <= 1 (which keeps
+                // the two floors within one cell) holds when c >= rp (1 + 3u) / (1 - 4.0002 u G): a margin of 1e-4 covers G <= 419 only.
+                // So the edge starts a hair above rp and is enlarged until the grid has at most BQ_MAXCELLS cells AND the margin
+                // covers its largest axis (2.5e-7 > 4.0002 u and 1.000001 > 1 + 3u leave room for the rounding of this test itself).
                 float c = rp * 1.0001f;
                 for (;;) {
                     inv_c = 1.0f / c;
@@ -159,6 +168,7 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void ball_query_kernel(int n, int m,
                         G[a] = (int)f + 1;                    // the point at hi[a] lands in cell G - 1 by the same operations
                         cells *= G[a];
                         if (cells > BQ_MAXCELLS) { fits = false; break; }
+                        if (c * (1.f - 2.5e-7f * (float)G[a]) < rp * 1.000001f) { fits = false; break; }
                     }
                     if (fits) break;
                     c *= 1.26f;
@@ -168,7 +178,8 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void ball_query_kernel(int n, int m,
                 const int cells = G[0] * G[1] * G[2];
                 auto key_of = [&](float x, float y, float z) {
                     int ix = (int)((x - glo[0]) * inv_c), iy = (int)((y - glo[1]) * inv_c), iz = (int)((z - glo[2]) * inv_c);
-                    ix = ix < 0 ? 0 : (ix >= G[0] ? G[0] - 1 : ix);      // (only a NaN coordinate is ever clamped)
+                    // (only a NaN coordinate is ever clamped; whatever the conversion makes of it, the clamp keeps the key inside the grid)
+                    ix = ix < 0 ? 0 : (ix >= G[0] ? G[0] - 1 : ix);
                     iy = iy < 0 ? 0 : (iy >= G[1] ? G[1] - 1 : iy);
                     iz = iz < 0 ? 0 : (iz >= G[2] ? G[2] - 1 : iz);
                     return (iz * G[1] + iy) * G[0] + ix;

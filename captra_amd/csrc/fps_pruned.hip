@@ -31,7 +31,8 @@
 // afterwards equalled it before), i.e. c IS the next pick, and so on down the sorted list.  A wave knows only its TOP point,
 // so the list is the NW wave tops, and a wave whose top was taken contributes an OBSTACLE instead: an upper bound on
 // everything else it holds (its second-largest bucket maximum, and the runner-up of the top's own bucket, kept per bucket
-// next to its maximum).  A candidate must beat, strictly, the obstacles of the waves already picked from.  The certification
+// next to its maximum; the top itself where a NaN / Inf coordinate keeps it from ever reaching distance 0).  A candidate must beat,
+// strictly, the obstacles of the waves already picked from.  The certification
 // runs on the 8 x 8 pairs of wave tops, one pair per lane, after the one barrier of the round (two ballots give every top
 // its predecessors and whether one of them spoils it); the picks are then applied together, each touched bucket read and
 // written once for all of them.  Picks are identical to the one-per-round kernel's (the same tests pass, incl.
@@ -303,8 +304,11 @@ __global__ __launch_bounds__(FP_NW * 64) void fps_pruned_kernel(int n_stride, co
         uint2 *slot = slots + (rounds & 1) * 16;
         float4 *sc = slotc + (rounds & 1) * 16;
         if (lane == li) {
+            // a top with a NaN or Inf coordinate is not at distance 0 from itself (NaN): picked, it KEEPS its running minimum and is
+            // the maximum again, as in the reference -- so it is its own wave's obstacle, and no later top is certified in its round
+            const bool keeps = __builtin_amdgcn_classf(bwx, 0x207) || __builtin_amdgcn_classf(bwy, 0x207) || __builtin_amdgcn_classf(bwz, 0x207);
             slot[wave] = make_uint2(bmax, boi);
-            sc[wave] = make_float4(bwx, bwy, bwz, __uint_as_float(obst));
+            sc[wave] = make_float4(bwx, bwy, bwz, __uint_as_float(keeps ? bmax : obst));
         }
         const unsigned long long t2 = STATS ? __builtin_amdgcn_s_memtime() : 0ull;
         __syncthreads();
