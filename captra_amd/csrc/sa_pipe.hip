@@ -13,7 +13,11 @@
 //      gather costs registers, not time).  v1 is read POINT-major (B,N,C1; written that way by captra_pointwise_mlp_pm):
 //      the four accumulator rows a lane needs are one 16-byte load, a slice touches 128 cache lines instead of up to 4096;
 //   2. every pass's epilogue is deferred by one pass and issued in parts behind the next pass's MFMA blocks (two
-//      accumulator pairs alternate), only a layer's last pass is exposed;
+//      accumulator pairs alternate), only a layer's last pass is exposed.  (Deferring that one too -- layer 1's ReLU + swap
+//      units behind layer 2's first pass, layer 2's last pass behind layer 3's first -- was built and measured 0.7 - 0.9 %
+//      SLOWER per launch on both shapes: DESIGN.md section 3.2);
+//   2b. layer 2 of the 196-wide shape runs its four rows beyond the last whole tile on the vector pipe (sp_body, REM):
+//      1176 MFMAs per 32-neighbour slice instead of 1240;
 //   3. weight sets stream two sets (2048 MFMA cycles) ahead through a ring of three;
 //   4. the last layer's maximum over the centre's slices stays in registers (a transpose-reduce butterfly per slice folded
 //      into a running maximum, sw_bfly_finish once per centre): no LDS, no barrier after start-up.  (Round 2 first staged
@@ -151,13 +155,26 @@ __device__ __forceinline__ void sp_epi_part(const f32x16 (&acc)[2], int ps, int 
 // ~16 cycles) exactly as busy as its matrix pipes (one MFMA per SIMD per 64 cycles): 19 % of a tile's cycles went into
 // waiting for weights that were in L2 all along (measured in round 2 with the weight loads compiled out).
 
+// One MFMA, then NV of the vector-pipe instructions issued with the block, sixteen times: each of them issues while an MFMA
+// executes (left to itself the scheduler puts them all behind the block, where only the last MFMA covers them)
+template <int NV>
+__device__ __forceinline__ void sp_interleave() {
+#pragma unroll
+    for (int i = 0; i < 2 * SW_KS; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x002, NV, 0);   // VALU
+    }
+}
+
 // One layer: hin[] (B operands) -> hout[] (LAST = false) or per-wave maxima in red (LAST = true).  Weight sets in the ring
 // s[3]: the set of step g is s[(START + g) % 3]; this layer's first set must already be on its way (previous phase), the
 // following layer's first set is requested through `next(s[(START + STEPS) % 3])` two steps before the end.  `side(g)` runs
 // once per step before the MFMA block (the kernel hangs the next tile's prefetch on it).
-template <int CIN, int COUT, bool LAST, int START, int NIN, int NOUT, int NZ, typename Next, typename Side>
+// `extra(g)` is vector-pipe work of the CALLER's that is issued with the MFMA blocks of the first XSTEPS steps, XV instructions per
+// MFMA (the remainder rows of sp_body).
+template <int CIN, int COUT, bool LAST, int START, int XSTEPS, int XV, int NIN, int NOUT, int NZ, typename Next, typename Side, typename Extra>
 __device__ __forceinline__ void sp_layer(const float *wt, const float *bias_lds, const float (&hin)[NIN], float (&hout)[NOUT],
-                                         float (&s)[3][16], int (&zrun)[NZ], int lane, Next next, Side side) {
+                                         float (&s)[3][16], int (&zrun)[NZ], int lane, Next next, Side side, Extra extra) {
     using S = SwShape<CIN, COUT>;
     static_assert(NIN >= S::KST, "input operand array too small");
     const __amdgpu_buffer_rsrc_t rsrc = sw_frag_rsrc<CIN, COUT>(wt);
@@ -186,17 +203,12 @@ __device__ __forceinline__ void sp_layer(const float *wt, const float *bias_lds,
                 if (kk < S::KST && 2 * ps + tm < S::NT)
                     acc[pb][tm] = __builtin_amdgcn_mfma_f32_32x32x2f32(s[(START + g) % 3][tm * SW_KS + j], hin[kk], acc[pb][tm], 0, 0, 0);
             }
-        // the previous pass's epilogue, one part per step: issued behind this step's MFMAs, it runs while they execute
-        if (ps > 0) {
-            sp_epi_part<COUT, LAST, S::NSETS>(acc[pb ^ 1], ps - 1, c, hout, zrun, mst, lane);
-            // one MFMA, then a few of the part's VALU instructions, sixteen times: each of them issues while an MFMA executes
-            // (left to itself the scheduler puts the whole part behind the block, where only the last MFMA covers it)
-#pragma unroll
-            for (int i = 0; i < 2 * SW_KS; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);   // VALU
-            }
-        }
+        // the caller's extra work and the previous pass's epilogue, one part per step: issued behind this step's MFMAs
+        if (g < XSTEPS) extra(g);
+        if (ps > 0) sp_epi_part<COUT, LAST, S::NSETS>(acc[pb ^ 1], ps - 1, c, hout, zrun, mst, lane);
+        if (ps > 0 && g < XSTEPS) sp_interleave<4 + XV>();
+        else if (ps > 0) sp_interleave<4>();
+        else if (g < XSTEPS) sp_interleave<XV>();
         __builtin_amdgcn_sched_barrier(0);
     }
     constexpr int LP = S::NPASS - 1;
@@ -207,18 +219,30 @@ __device__ __forceinline__ void sp_layer(const float *wt, const float *bias_lds,
 // (the kernel's body as a device function of (workgroup, workgroups): sa_wave_pipe2_kernel runs the level's two scales in one launch)
 template <int CF, int C1, int C2, int C3>
 __device__ __forceinline__ void sp_body(const SpParams &p, const int blk, const int nblk) {
+    // REM: layer 2 has four rows beyond its last whole 32-row tile (C2 = 196).  A seventh MFMA tile would multiply 28 zero weight
+    // rows (64 of a slice's 1240 MFMAs); instead the matrix pipe takes the C2M = C2 - 4 rows of the whole tiles and the vector pipe
+    // the other four behind layer 2's first pass: lane-half h carries rows C2M + 2h and C2M + 2h + 1 of the slice's 32 positions
+    // as two v_fma_f32 chains from the bias, k ascending -- the chain the MFMA runs (generated and handed-on NaNs, subnormals and
+    // overflow come out of v_fma_f32 with the MFMA's bits), so every output keeps its bits.
+    constexpr bool REM = C2 % 32 == 4;
+    constexpr int C2M = REM ? C2 - 4 : C2;
     using S1 = SwShape<CF + 3, C1>;
-    using S2 = SwShape<C1, C2>;
+    using S2 = SwShape<C1, C2M>;       // (C2M and C2 pad to the same 128 columns: the same packed images)
     using S3 = SwShape<C2, C3>;
     constexpr int NT1 = S1::NT;
     static_assert(NT1 <= 4 && C1 % 32 == 0, "first-layer width");
+    static_assert(pad128c(C2M) == pad128c(C2) && S2::KST % SW_KS == 0, "layer-2 shape");
     __shared__ __attribute__((aligned(16))) float bias_lds[2 * 256];       // packed b2, b3 (zero padded)
+    __shared__ __attribute__((aligned(16))) float rem_w[REM ? 4 * C1 : 4];  // W2 rows C2M..C2M+3, a row's C1 weights consecutive
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     for (int e = tid; e < 2 * 256; e += 256) {
         const int c = e & 255;
         bias_lds[e] = e < 256 ? (c < pad128c(C2) ? p.b2[c] : 0.f) : (c < pad128c(C3) ? p.b3[c] : 0.f);
+    }
+    if constexpr (REM) {
+        for (int e = tid; e < 4 * C1; e += 256) rem_w[(e & 3) * C1 + (e >> 2)] = p.w2[(size_t)(e >> 2) * S2::LDW + C2M + (e & 3)];   // (row-major image)
     }
     // first layer's xyz rows of W1 (A operands of its two k-steps): the same for every slice
     float at[2][NT1];
@@ -326,17 +350,61 @@ __device__ __forceinline__ void sp_body(const SpParams &p, const int blk, const 
 #pragma unroll
             for (int t = 0; t < NT1; ++t) sw_mid_epilogue<S2::KST>(acc[t], t, h1);
         }
+        // ---- the remainder rows (REM): weights of a k-step set one set ahead in registers, two chains per lane ----
+        float4 rw[2][REM ? SW_KS : 1];
+        float racc[2] = {0.f, 0.f};
+        auto rem_load = [&](int c) {                    // the lane's two rows' weights for input rows 16c..16c+15
+            if constexpr (REM) {
+                const float4 *wp = reinterpret_cast<const float4 *>(rem_w + 2 * half * C1 + 2 * SW_KS * c);
+#pragma unroll
+                for (int i = 0; i < SW_KS; ++i) rw[c & 1][i] = wp[(i >> 2) * (C1 / 4) + (i & 3)];
+            }
+        };
+        auto rem_step = [&](int c) {                    // k-steps 8c..8c+7: per k-step one swap (input row 2kk, then 2kk+1, in every lane) and four fmaf
+            if constexpr (REM) {
+#pragma unroll
+                for (int j = 0; j < SW_KS; ++j) {
+                    const unsigned hb = __float_as_uint(h1[SW_KS * c + j]);
+                    const auto eo = __builtin_amdgcn_permlane32_swap(hb, hb, false, false);
+                    const float he = __uint_as_float(eo[0]), ho = __uint_as_float(eo[1]);
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        const float4 w4 = rw[c & 1][4 * r + (j >> 1)];
+                        racc[r] = __builtin_fmaf((j & 1) ? w4.z : w4.x, he, racc[r]);
+                        racc[r] = __builtin_fmaf((j & 1) ? w4.w : w4.y, ho, racc[r]);
+                    }
+                }
+                if (c == S2::NSETS - 1) {
+                    // sp_mid_unit's ReLU; half h holds rows (C2M + 2h, C2M + 2h + 1), layer 3's k-step C2M / 2 + i wants row C2M + 2i + h
+                    const int x0 = __float_as_int(racc[0]), x1 = __float_as_int(racc[1]);
+                    const auto pr = __builtin_amdgcn_permlane32_swap((unsigned)(x0 > 0 ? x0 : 0), (unsigned)(x1 > 0 ? x1 : 0), false, false);
+                    h2[C2M / 2] = __uint_as_float(pr[0]);
+                    h2[C2M / 2 + 1] = __uint_as_float(pr[1]);
+                }
+            }
+        };
+        if constexpr (REM) {
+            racc[0] = bias_lds[C2M + 2 * half];
+            racc[1] = bias_lds[C2M + 2 * half + 1];
+            rem_load(0);
+        }
         __builtin_amdgcn_sched_barrier(0);
         SP_TICK(1)
-        // ---- layer 2; its second step asks for the next slice's neighbour ids ----
-        sp_layer<C1, C2, false, 0>(p.w2, bias_lds, h1, h2, s, zrun, lane,
+        // ---- layer 2 (the whole tiles); its second step asks for the next slice's neighbour ids; the remainder rows' k-steps
+        // 8g..8g+7 are issued with the MFMAs of step g of the first pass, which consume the same H1 registers ----
+        sp_layer<C1, C2M, false, 0, REM ? S2::NSETS : 0, 5>(p.w2, bias_lds, h1, h2, s, zrun, lane,
                                    [&](float (&dst)[16]) { sw_first_set<C2, C3>(dst, p.w3, lane); },
-                                   [&](int g) { if (g == 1 && has_next) id_n = load_id(cn, sn); });
+                                   [&](int g) {
+                                       if (g == 1 && has_next) id_n = load_id(cn, sn);
+                                       if (g + 1 < S2::NSETS) rem_load(g + 1);
+                                   },
+                                   [&](int g) { rem_step(g); });
         SP_TICK(2)
         // ---- layer 3 + running max over the slices; its third step gathers the next slice's start values ----
-        sp_layer<C2, C3, true, START3>(p.w3, bias_lds + 256, h2, none, s, zrun, lane,
+        sp_layer<C2, C3, true, START3, 0, 0>(p.w3, bias_lds + 256, h2, none, s, zrun, lane,
                                        [&](float (&dst)[16]) { sw_first_set<C1, C2>(dst, p.w2, lane); },
-                                       [&](int g) { if (g == 2 && has_next) load_rest(cn, id_n, bt, g4); });
+                                       [&](int g) { if (g == 2 && has_next) load_rest(cn, id_n, bt, g4); },
+                                       [](int) {});
         id = id_n;
         SP_TICK(3)
         if (CAPTRA_PROF_ON(p.prof) && lane == 0 && sampled) atomicAdd(p.prof + 9, 1ull);
