@@ -226,13 +226,43 @@ __device__ __forceinline__ int otf_list_length(int c, int num_points) {
     return len;
 }
 
+// THIN (captra_otf_candidates_thin / captra_otf_finish_thin): a row whose thinned[b] is set takes its list from table (B, 5 num_points),
+// the ascending member numbers captra_otf_thin (csrc/otf_thin.hip) selected -- candidate j = member table[b][j], length 5 num_points,
+// rare only when that outgrows the stride (the list is then the table's first `stride` entries), info[2] counts such rows.  As with
+// crop_ball_kernel<DET>, the two extra parameters come LAST and the plain instantiation does not touch them.
+template <bool THIN>
 __global__ __launch_bounds__(256) void otf_candidates_kernel(int cap, int stride, int num_points, const double *__restrict__ pts,
                                                              const int *__restrict__ counts, float *__restrict__ cand,
-                                                             int *__restrict__ lens, int *__restrict__ info) {
+                                                             int *__restrict__ lens, int *__restrict__ info,
+                                                             const int *__restrict__ table, const int *__restrict__ thinned) {
     const int b = blockIdx.y;
     const int c = counts[b * 2];
     const int lim = cap < stride ? cap : stride;                    // members a list may name: what the table holds, at most a stride
     const int cc = c < 1 ? 1 : (c > lim ? lim : c);                 // rare rows clamped: every access stays inside its instance's table
+    if constexpr (THIN) {
+        if (thinned[b] != 0) {
+            const double *pb = pts + (size_t)b * cap * 3;
+            float *cb = cand + (size_t)b * stride * 3;
+            const int t_keep = 5 * num_points;
+            const int keep = t_keep < stride ? t_keep : stride;
+            if (blockIdx.x == 0 && threadIdx.x == 0) {
+                lens[b] = keep;
+                if (t_keep > stride) atomicOr(info, 1);
+                atomicMax(info + 1, t_keep);
+                atomicAdd(info + 2, 1);
+            }
+            const int *tb = table + (size_t)b * t_keep;
+            for (int j = blockIdx.x * 256 + threadIdx.x; j < stride; j += gridDim.x * 256) {
+                float x = 0.f, y = 0.f, z = 0.f;
+                if (j < keep) {
+                    const double *q = pb + (size_t)tb[j] * 3;
+                    x = (float)q[0]; y = (float)q[1]; z = (float)q[2];
+                }
+                cb[(size_t)j * 3 + 0] = x; cb[(size_t)j * 3 + 1] = y; cb[(size_t)j * 3 + 2] = z;
+            }
+            return;
+        }
+    }
     const int len = otf_list_length(cc, num_points);
     const int keep = len < stride ? len : stride;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -252,18 +282,26 @@ __global__ __launch_bounds__(256) void otf_candidates_kernel(int cap, int stride
     }
 }
 
+template <bool THIN>
 __global__ __launch_bounds__(256) void otf_finish_kernel(int cap, int stride, int n, const double *__restrict__ pts,
                                                          const unsigned char *__restrict__ obj, const int *__restrict__ counts,
                                                          const int *__restrict__ picks, const float *__restrict__ mean,
                                                          const double *__restrict__ rot, const double *__restrict__ trans,
                                                          const double *__restrict__ scale, float *__restrict__ points_cn,
-                                                         long long *__restrict__ labels, float *__restrict__ nocs_cn) {
+                                                         long long *__restrict__ labels, float *__restrict__ nocs_cn,
+                                                         const int *__restrict__ table, const int *__restrict__ thinned) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int c = counts[b * 2];
     const int lim = cap < stride ? cap : stride;
     const int cc = c < 1 ? 1 : (c > lim ? lim : c);                   // otf_candidates_kernel's clamp
-    const int m = picks[(size_t)b * n + i] % cc;                      // candidate -> member
+    int m = picks[(size_t)b * n + i] % cc;                            // candidate -> member
+    if constexpr (THIN) {
+        if (thinned[b] != 0) {                                        // a thinned row: through its table of 5 n members (a pick stays inside it)
+            const int p = picks[(size_t)b * n + i];
+            m = table[(size_t)b * 5 * n + (p < 0 ? 0 : (p < 5 * n ? p : 5 * n - 1))];
+        }
+    }
     const double *q = pts + ((size_t)b * cap + m) * 3;
     const bool o = obj[(size_t)b * cap + m] != 0;
     const double *R = rot + (size_t)b * 9, *t = trans + (size_t)b * 3;
@@ -333,8 +371,20 @@ extern "C" int captra_otf_candidates(int b, int cap, int stride, int num_points,
     if (b < 0 || cap < 1 || stride < 1 || num_points < 1 || num_points > stride) return -1;
     if (b == 0) return 0;
     if (captra_zero_async(info, 16, (hipStream_t)stream) != 0) return -1;
-    CAPTRA_LAUNCH("crop_ball", otf_candidates_kernel, dim3((unsigned)((stride + 1023) / 1024), b), dim3(256), 0, (hipStream_t)stream, cap, stride,
-                  num_points, pts, counts, cand, lens, info);
+    CAPTRA_LAUNCH("crop_ball", otf_candidates_kernel<false>, dim3((unsigned)((stride + 1023) / 1024), b), dim3(256), 0, (hipStream_t)stream, cap, stride,
+                  num_points, pts, counts, cand, lens, info, (const int *)nullptr, (const int *)nullptr);
+    return captra_last_error();
+}
+
+// captra_otf_candidates with the rows flagged in thinned (B,) taking their lists from table (B, 5 num_points) (captra_otf_thin's outputs);
+// info[2] = the number of such rows.  With thinned all zero: captra_otf_candidates' outputs.
+extern "C" int captra_otf_candidates_thin(int b, int cap, int stride, int num_points, const double *pts, const int *counts, float *cand,
+                                          int *lens, int *info, const int *table, const int *thinned, captra_stream_t stream) {
+    if (b < 0 || cap < 1 || stride < 1 || num_points < 1 || num_points > stride || num_points > 0x7fffffff / 5) return -1;
+    if (b == 0) return 0;
+    if (captra_zero_async(info, 16, (hipStream_t)stream) != 0) return -1;
+    CAPTRA_LAUNCH("crop_ball", otf_candidates_kernel<true>, dim3((unsigned)((stride + 1023) / 1024), b), dim3(256), 0, (hipStream_t)stream, cap, stride,
+                  num_points, pts, counts, cand, lens, info, table, thinned);
     return captra_last_error();
 }
 
@@ -345,7 +395,19 @@ extern "C" int captra_otf_finish(int b, int cap, int stride, int n, const double
                                  float *points_cn, long long *labels, float *nocs_cn, captra_stream_t stream) {
     if (b < 0 || cap < 1 || stride < 1 || n < 1) return -1;
     if (b == 0) return 0;
-    CAPTRA_LAUNCH("crop_ball", otf_finish_kernel, dim3((unsigned)((n + 255) / 256), b), dim3(256), 0, (hipStream_t)stream, cap, stride, n, pts, obj,
-                  counts, picks, mean, rot, trans, scale, points_cn, labels, nocs_cn);
+    CAPTRA_LAUNCH("crop_ball", otf_finish_kernel<false>, dim3((unsigned)((n + 255) / 256), b), dim3(256), 0, (hipStream_t)stream, cap, stride, n, pts, obj,
+                  counts, picks, mean, rot, trans, scale, points_cn, labels, nocs_cn, (const int *)nullptr, (const int *)nullptr);
+    return captra_last_error();
+}
+
+// captra_otf_finish with a pick p of a row flagged in thinned (B,) read as member table[b][p] of table (B, 5 n).
+extern "C" int captra_otf_finish_thin(int b, int cap, int stride, int n, const double *pts, const unsigned char *obj, const int *counts,
+                                      const int *picks, const float *mean, const double *rot, const double *trans, const double *scale,
+                                      float *points_cn, long long *labels, float *nocs_cn, const int *table, const int *thinned,
+                                      captra_stream_t stream) {
+    if (b < 0 || cap < 1 || stride < 1 || n < 1 || n > 0x7fffffff / 5) return -1;
+    if (b == 0) return 0;
+    CAPTRA_LAUNCH("crop_ball", otf_finish_kernel<true>, dim3((unsigned)((n + 255) / 256), b), dim3(256), 0, (hipStream_t)stream, cap, stride, n, pts, obj,
+                  counts, picks, mean, rot, trans, scale, points_cn, labels, nocs_cn, table, thinned);
     return captra_last_error();
 }

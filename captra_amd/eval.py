@@ -131,6 +131,13 @@ def rot_pool_table(name: str, data: dict) -> list:
     return lines
 
 
+def otf_thin_table(name: str, data: dict) -> list:
+    """The re-crop's on-device thinning record of one result pickle (present when the run had track_cfg/otf_thin/device): one line
+    with the frames whose candidate list was thinned, of the frames re-cropped."""
+    frames = [(i, int(np.asarray(r["thinned"]).reshape(-1)[0])) for i, r in enumerate(data["otf_thin"]) if r is not None and "thinned" in r]
+    return [f"{name}: thinned {sum(1 for _, t in frames if t != 0)} / {len(frames)} frames"]
+
+
 def write_csv(errors: dict, path: str) -> None:
     keys = list(next(iter(errors.values())).keys())
     with open(path, "w") as f:
@@ -156,7 +163,7 @@ def main(argv=None) -> dict:
     del args.eval_device
     cfg = get_config(args, save=False)
     data_path = pjoin(cfg["experiment_dir"], "results", "data")
-    errors, guard_lines, guard_tests, st_lines, rot_lines = {}, [], set(), [], []
+    errors, guard_lines, guard_tests, st_lines, rot_lines, thin_lines = {}, [], set(), [], [], []
     for raw in sorted(os.listdir(data_path)):
         with open(pjoin(data_path, raw), "rb") as f:
             data = pickle.load(f)
@@ -168,6 +175,8 @@ def main(argv=None) -> dict:
             st_lines += st_fit_table(raw.rsplit(".", 1)[0], data)
         if "rot_pool" in data:
             rot_lines += rot_pool_table(raw.rsplit(".", 1)[0], data)
+        if "otf_thin" in data:
+            thin_lines += otf_thin_table(raw.rsplit(".", 1)[0], data)
     if not errors:
         raise SystemExit(f"no result pickles under {data_path}")
     err_path = pjoin(cfg["experiment_dir"], "results", "err.pkl")
@@ -188,6 +197,10 @@ def main(argv=None) -> dict:
     if rot_lines:
         print("consensus rotation read-out (track_cfg/rot_pool), per trajectory and part:")
         for line in rot_lines:
+            print("  " + line)
+    if thin_lines:
+        print("re-crop lists thinned on the device (track_cfg/otf_thin), frames per trajectory:")
+        for line in thin_lines:
             print("  " + line)
     return avg
 

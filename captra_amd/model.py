@@ -152,6 +152,13 @@ class EvalTrackModel(BaseModel):
         # no pickle entry.
         self.rot_pool = self.net.rot_pool = self._rot_pool_cfg(cfg)
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
+        # track_cfg: {otf_thin: {device: True, seed: <int>}}: the re-crop thins a candidate list of more than 5 N ball members ON THE
+        # DEVICE (csrc/otf_thin.hip: a counter-based draw keyed by seed, trajectory and frame, the kept members in pixel order -- not
+        # numpy's permutation, see include/captra_hip.h) instead of on the host, so a close-up crop is no rare-path instance of the
+        # sync-free loop; the frames' thinned instances are recorded (pred_dict / pickle 'otf_thin').  Absent / device: False: nothing
+        # is launched, no tensor, no pickle entry, numpy's generator is consumed as before.
+        self.otf_thin = self._otf_thin_cfg(cfg)
+        self._otf_thin_rec = {}             # frame -> {first trajectory of a slice: its thinned flags (b,) int32 on the device}
         self.radius = cfg["data_radius"]
         self.det_category = cfg["obj_category"]          # nocs2d_label: the class id the frame's detections are matched against
         self._det_missing_logged = False
@@ -233,6 +240,17 @@ class EvalTrackModel(BaseModel):
         if seed < 0:
             raise ValueError(f"track_cfg/st_fit/seed must not be negative, got {seed}")
         return {"inlier_th": frac * float(cfg["data_radius"]), "num_hyps": num_hyps, "seed": seed}
+
+    @staticmethod
+    def _otf_thin_cfg(cfg):
+        """track_cfg/otf_thin, parsed once: None when absent or device is not set, else {'seed'}."""
+        t = cfg["track_cfg"].get("otf_thin")
+        if t is None or not t.get("device", False):
+            return None
+        seed = int(t.get("seed", 0) or 0)
+        if seed < 0:
+            raise ValueError(f"track_cfg/otf_thin/seed must not be negative, got {seed}")
+        return {"seed": seed}
 
     @staticmethod
     def _rot_pool_cfg(cfg):
@@ -600,13 +618,21 @@ class EvalTrackModel(BaseModel):
         gtd = input.get("gt_root_dev")
         gtd = None if gtd is None else {k: v[sl] for k, v in gtd.items()}
         trans_d, scale_d = last_pose["translation"][:, self.root].reshape(b, 3), last_pose["scale"][:, self.root].reshape(b)
+        # track_cfg/otf_thin: keyed by the trajectory's place in the whole batch and the frame, so that a lane draws what the whole
+        # batch draws and a replayed frame what its first run drew
+        thin = None if self.otf_thin is None else (self.otf_thin["seed"], i, sl.start or 0)
         if (OTF_POSE_ON_DEVICE or det is not None) and depth.is_cuda and trans_d.dtype == torch.float32 and scale_d.dtype == torch.float32:
             # the crop's box / centre / radius derived on the device from the pose (captra_crop_box): no round trip for the pose
             # (the detector route exists in this form only: its selection is captra_crop_box_det)
             full = full_data_batch_arrays(depth, mask, None, None, gt64, N, stacked=True, pose_dev=(trans_d, scale_d, float(self.radius)), gt_dev=gtd,
-                                          defer=defer, mean=npcs["points_mean"][sl], det=det)
+                                          defer=defer, mean=npcs["points_mean"][sl], det=det, thin=thin)
+            if thin is not None:
+                self._otf_thin_rec.setdefault(i, {})[sl.start or 0] = full["_thinned"]     # (a replay of the frame puts its own in place)
             if defer is not None:
                 return full["points_cn"], full["labels"], full["nocs_cn"], full["_info"]
+        elif thin is not None:
+            raise ValueError("track_cfg/otf_thin/device thins the re-crop's lists on the device: it needs the frames and an fp32 pose there "
+                             "(CUDA tensors, CAPTRA_OTF_POSE_ON_DEVICE not 0)")
         elif det is not None:
             raise ValueError("track_cfg/nocs2d_label with detections in the frame: the selection runs on the device from an fp32 pose")
         else:
@@ -797,6 +823,7 @@ class EvalTrackModel(BaseModel):
         guard = {}                          # frame -> its guard record (guard on)
         st_fit = {}                         # frame -> the robust fit's record (track_cfg/st_fit on)
         rot_pool = {}                       # frame -> the consensus read-out's record (track_cfg/rot_pool on)
+        self._otf_thin_rec = {}
         if self.frame_hook is not None:
             self.frame_hook(0, pred_poses[0])
         self.timer.tick()
@@ -829,6 +856,9 @@ class EvalTrackModel(BaseModel):
                         return [longest for _, longest in verdicts]
                     result, poses, _ = run_frame(pi, pin, [None] * len(bounds))
                     npcs_pred[pi], pred_poses[pi] = commit(pi, result)
+                    if self.otf_thin is not None:
+                        # a bound outgrown is outgrown ONCE: the next frame's bound follows the verdicts' longest lists
+                        return [longest for _, longest in verdicts]
                     return []
 
                 for i in range(1, len(feed)):
@@ -858,6 +888,11 @@ class EvalTrackModel(BaseModel):
             self.pred_dict["st_fit"] = [None] + [st_fit[i] for i in range(1, len(feed))]
         if self.rot_pool is not None:
             self.pred_dict["rot_pool"] = [None] + [rot_pool[i] for i in range(1, len(feed))]
+        if self.otf_thin is not None and self.nocs_otf:
+            # per frame: which trajectories' lists were thinned, (B,) int32 -- its sum is the frame's count of thinned instances
+            rec = self._otf_thin_rec
+            self.pred_dict["otf_thin"] = [None] + [next(iter(rec[i].values())) if len(rec[i]) == 1 else torch.cat([rec[i][k] for k in sorted(rec[i])])
+                                                   for i in range(1, len(feed))]
         self.check_l1_stream()
         if save:
             self._save(list(map(_frame_names, feed)))
@@ -907,6 +942,8 @@ class EvalTrackModel(BaseModel):
             save_dict["st_fit"] = [None if r is None else {k: v.detach().cpu().numpy() for k, v in r.items()} for r in self.pred_dict["st_fit"]]
         if self.rot_pool is not None:
             save_dict["rot_pool"] = [None if r is None else {k: v.detach().cpu().numpy() for k, v in r.items()} for r in self.pred_dict["rot_pool"]]
+        if "otf_thin" in self.pred_dict:
+            save_dict["otf_thin"] = [None if r is None else {"thinned": r.detach().cpu().numpy()} for r in self.pred_dict["otf_thin"]]
         records = []
         for i, path in enumerate(self.feed_dict[0]["meta"]["path"]):
             instance, track_num = path.split(".")[-2].split("/")[-3:-1]

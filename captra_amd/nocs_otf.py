@@ -11,7 +11,8 @@ furthest-point sampling is captra_fps_gather, and the host only sees three scala
 
 Ordering contract (it decides which point FPS starts from): candidate pixels in row-major image order, ball members in
 that order, duplication by whole-list doubling, the > 5 x num_points thinning by `numpy.random.permutation` (drawn on the
-host from numpy's global generator, as the reference does, so that seeded runs agree).
+host from numpy's global generator, as the reference does, so that seeded runs agree) -- or, opt-in, on the device by a rule
+of this build's own (full_data_batch_arrays' `thin`, include/captra_hip.h: captra_otf_thin).
 """
 from __future__ import annotations
 
@@ -254,7 +255,7 @@ DET_KEYS = ("det_boxes", "det_class", "det_count", "det_masks")
 
 
 def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, intrinsics=NOCS_REAL_INTRINSICS, stacked: bool = True,
-                           pose_dev=None, gt_dev=None, defer=None, mean=None, det=None):
+                           pose_dev=None, gt_dev=None, defer=None, mean=None, det=None, thin=None):
     """full_data_batch on already-stacked inputs (the track loop's form: no per-trajectory Python on the frame's critical
     path): depth (B,H,W), mask (B,H,W) device tensors; centers (B,3), radii_in (B,) float64 host arrays (radius as handed to
     full_data_from_depth: clamped to 0.05 inside); gt = {'rotation' (B,3,3), 'translation' (B,3), 'scale' (B,)} float64 host arrays.
@@ -269,9 +270,18 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
     `det` (with pose_dev) = the detector route (reference nocs_data_process.py:206-229, `nocs2d_label`): {'det_boxes' (B,K,4) int32
     [y1,x1,y2,x2], 'det_class' (B,K) int32, 'det_count' (B,) int32, 'det_masks' (B,K,H,W) uint8, 'category' int} device tensors -- every
     trajectory crops with the mask of the detection of its category that overlaps its (grown) box best (captra_crop_box_det selects,
-    captra_crop_ball_det reads that mask: two launches in place of two, nothing visits the host), `mask` where there is none."""
+    captra_crop_ball_det reads that mask: two launches in place of two, nothing visits the host), `mask` where there is none.
+    `thin` = (seed, frame, b0) (on the device only): a list of more than 5 num_points members is thinned ON THE DEVICE by
+    captra_otf_thin's rule (include/captra_hip.h: a counter-based draw keyed by seed, trajectory b0 + row and frame; the kept members
+    in ascending order -- NOT the reference's permutation) instead of by numpy.random.permutation, in both stages: with `defer` the
+    launch sits between the crop and the candidate launch and such an instance is no rare-path instance; on the synchronous stage the
+    same launch fills the row's table and nothing is drawn from numpy for it, so both stages produce the same clouds bit for bit.
+    Instances on the torch path (fewer than 10 members or more than CROP_CAP: crop_candidates) keep the host's permutation.  The
+    stacked results then carry '_thinned' (B,) int32: which instances were thinned."""
     from . import _lib as L, fused
     dev = depth.device
+    if thin is not None and dev.type != "cuda":
+        raise ValueError("thinning on the device (thin=(seed, frame, b0)) needs the frame on the device")
     B = depth.shape[0]
     depth = depth.to(torch.int32).contiguous()
     mask = mask.to(torch.uint8).contiguous()
@@ -329,6 +339,16 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
         with torch.cuda.device(dev):
             L.call("captra_crop_ball", B, H, W, CROP_CAP, L.ptr(depth), L.ptr(mask), hp + 8 * ndbl, hp,
                    hp + 8 * 3 * B, hp + 8 * 4 * B, L.ptr(pts), L.ptr(obj), L.ptr(pix), L.ptr(counts))
+    table_t = thinned_t = None
+    if thin is not None:
+        # the thinning launch (a workgroup per instance, which leaves at once when its list is not over-long): behind the crop in BOTH
+        # stages, with the same (seed, frame, b0 + row), so that a frame run again on the synchronous stage thins as its first run did
+        seed, frame, b0 = (int(x) for x in thin)
+        buf = torch.empty(B * (5 * num_points + 1), dtype=torch.int32, device=dev)         # (one allocation: the table, then the flags)
+        table_t, thinned_t = buf[:B * 5 * num_points].view(B, 5 * num_points), buf[B * 5 * num_points:]
+        with torch.cuda.device(dev):
+            L.call("captra_otf_thin", B, CROP_CAP, num_points, b0, frame & 0xFFFFFFFF, seed & 0xFFFFFFFFFFFFFFFF, L.ptr(counts), None,
+                   L.ptr(table_t), L.ptr(thinned_t))
     if defer is not None and pose_dev is not None:
         # ---- NO round trip: the candidate lists' lengths, the member table and the ragged sampler's
         # per-cloud counts are derived from the crop's counts ON THE DEVICE; the sampler's padded stride is an upper bound the
@@ -342,7 +362,11 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
         lens = torch.empty(B, dtype=torch.int32, device=dev)
         info = torch.empty(4, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            L.call("captra_otf_candidates", B, CROP_CAP, stride, num_points, L.ptr(pts), L.ptr(counts), L.ptr(cand), L.ptr(lens), L.ptr(info))
+            if thin is not None:
+                L.call("captra_otf_candidates_thin", B, CROP_CAP, stride, num_points, L.ptr(pts), L.ptr(counts), L.ptr(cand), L.ptr(lens), L.ptr(info),
+                       L.ptr(table_t), L.ptr(thinned_t))
+            else:
+                L.call("captra_otf_candidates", B, CROP_CAP, stride, num_points, L.ptr(pts), L.ptr(counts), L.ptr(cand), L.ptr(lens), L.ptr(info))
         res = fused.fps_gather(cand, num_points, n_per_cloud=lens)
         if gt_dev is not None:
             rot, trans, scale = (gt_dev["rotation"].reshape(B, 3, 3).contiguous(), gt_dev["translation"].reshape(B, 3).contiguous(),
@@ -356,6 +380,10 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
         labels = torch.empty(B, num_points, dtype=torch.int64, device=dev)
         nocs_cn = torch.empty(B, 3, num_points, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
+            if thin is not None:
+                L.call("captra_otf_finish_thin", B, CROP_CAP, stride, num_points, L.ptr(pts), L.ptr(obj), L.ptr(counts), L.ptr(res[0]), L.ptr(mean_d),
+                       L.ptr(rot), L.ptr(trans), L.ptr(scale), L.ptr(points_cn), L.ptr(labels), L.ptr(nocs_cn), L.ptr(table_t), L.ptr(thinned_t))
+                return {"points_cn": points_cn, "labels": labels, "nocs_cn": nocs_cn, "_info": info, "_thinned": thinned_t}
             L.call("captra_otf_finish", B, CROP_CAP, stride, num_points, L.ptr(pts), L.ptr(obj), L.ptr(counts), L.ptr(res[0]), L.ptr(mean_d),
                    L.ptr(rot), L.ptr(trans), L.ptr(scale), L.ptr(points_cn), L.ptr(labels), L.ptr(nocs_cn))
         return {"points_cn": points_cn, "labels": labels, "nocs_cn": nocs_cn, "_info": info}
@@ -387,7 +415,8 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
         while length < num_points:
             length *= 2
         if length > 5 * num_points:
-            perms[b] = np.random.permutation(length)[:5 * num_points]
+            # (thin: the row of table_t the launch above filled -- no draw from numpy)
+            perms[b] = None if thin is not None else np.random.permutation(length)[:5 * num_points]
             length = 5 * num_points
         lengths[b] = length
     fast = [b for b in range(B) if lengths[b] > 0]
@@ -400,7 +429,7 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
         table_d = torch.arange(max(lens), device=dev).unsqueeze(0) % cnt_f.unsqueeze(1)
         for i, b in enumerate(fast):
             if b in perms:
-                table_d[i, :lens[i]] = to_device(perms[b], dev) % cnt_f[i]
+                table_d[i, :lens[i]] = table_t[b].long() if perms[b] is None else to_device(perms[b], dev) % cnt_f[i]
         if len(fast) == B:
             pts_f, obj_f = pts, obj
         else:
@@ -422,11 +451,13 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
         nocs = torch.where(O.unsqueeze(-1), torch.bmm((P - trans) / scale.reshape(-1, 1, 1), rot), torch.zeros_like(P))
         labels = 1 - O.long()
         if stacked and len(fast) == B:
-            return {"points": P, "labels": labels, "nocs": nocs}
+            return {"points": P, "labels": labels, "nocs": nocs, **({} if thin is None else {"_thinned": thinned_t})}
         for i, b in enumerate(fast):
             out[b] = {"points": P[i], "labels": labels[i], "nocs": nocs[i]}
     for b, (p_all, raw_mask, idx, perm) in slow.items():
         picked = _device_fps(_candidate_cloud(p_all, idx, perm), num_points)
         sel_b = idx[perm[picked] if perm is not None else picked]
         out[b] = _full_data(p_all[sel_b], raw_mask[sel_b], gt_of(b))
+    if stacked and thin is not None:
+        return {**stack_full_data(out), "_thinned": thinned_t}
     return stack_full_data(out) if stacked else out

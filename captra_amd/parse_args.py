@@ -36,6 +36,8 @@ _FLAGS = [  # (name, type, default)
     # (degrees) is required
     ("track_cfg/rot_pool/consensus", boolean_string, None), ("track_cfg/rot_pool/angle_th", float, None),
     ("track_cfg/rot_pool/num_hyps", int, None), ("track_cfg/rot_pool/seed", int, None),
+    # the re-crop's over-long candidate lists thinned on the device (model.py: EvalTrackModel.otf_thin); off unless device is True
+    ("track_cfg/otf_thin/device", boolean_string, None), ("track_cfg/otf_thin/seed", int, None),
     # optimisation
     ("total_epoch", int, None), ("optimizer", str, None), ("weight_decay", float, None), ("learning_rate", float, None),
     ("lr_policy", str, None), ("lr_gamma", float, None), ("lr_step_size", int, None), ("lr_clip", float, None), ("freq/save", int, None),

@@ -168,16 +168,17 @@ PHYSICAL_SETUPS_MORE = {
 }
 
 # ---- depth frames (the on-the-fly re-crop's input) -----------------------------------------------------------------------
-def make_frame(seed: int, height: int = 480, width: int = 640, dr: float = 0.0, dc: float = 0.0):
+def make_frame(seed: int, height: int = 480, width: int = 640, dr: float = 0.0, dc: float = 0.0, blob_px: float = 70):
     """Synthetic depth frame (uint16 mm) with an object blob in front of a wavy background, its mask, a predicted centre
     and radius, and an instance pose.  (dr, dc): the blob displaced by that many pixel rows / columns -- a moving object over
-    the frames of a trajectory; the defaults are golden G11's frames."""
+    the frames of a trajectory; the defaults are golden G11's frames.  blob_px: the blob's radius in pixels (70: about 15 100 ball
+    members at the tracking radius; 90: a close-up of about 24 950, more than the 5 x 4096 an unthinned candidate list holds)."""
     rng = np.random.default_rng(seed)
     r, c = np.mgrid[0:height, 0:width]
     depth = 1500.0 + 80.0 * np.sin(r / 37.0) + 60.0 * np.cos(c / 53.0)
     cr, cc = 200 + 40 * rng.random() + dr, 300 + 60 * rng.random() + dc
     rr = np.sqrt((r - cr) ** 2 + (c - cc) ** 2)
-    blob = rr < 70
+    blob = rr < blob_px
     depth[blob] = 900.0 + 0.004 * rr[blob] ** 2 + 20.0 * np.sin(c[blob] / 9.0)
     depth[rng.random(depth.shape) < 0.02] = 0.0                       # holes
     depth = depth.astype(np.uint16)
@@ -332,15 +333,16 @@ def make_physical_state_dict(shapes: dict, seed: int, num_parts: int, sym: bool,
     return sd
 
 
-def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float = 6.0):
+def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float = 6.0, blob_px: float = 70):
     """A trajectory for the on-the-fly re-crop loop (`nocs_otf=True`, reference model.py:425-452): the frame dicts of
     make_trajectory('nocs', ...) carrying, per frame, the depth image / instance mask the loop re-crops
     (meta['pre_fetched']) and the blob's ground-truth pose (meta['nocs2camera']); trajectory b watches depth frame
     make_frame(seed + b) whose blob drifts by `step_px` pixels per time step.  Also the reference's path conventions
-    (meta['path'] = .../<category>/<instance>/<track>/<frame>.npz, meta['ori_path'])."""
+    (meta['path'] = .../<category>/<instance>/<track>/<frame>.npz, meta['ori_path']).  blob_px: make_frame's (90 = the close-up whose
+    candidate lists are thinned)."""
     data = make_trajectory("nocs", batch, frames, seed=seed)
     for t, f in enumerate(data):
-        views = [make_frame(seed + b, dr=0.5 * step_px * t, dc=step_px * t) for b in range(batch)]
+        views = [make_frame(seed + b, dr=0.5 * step_px * t, dc=step_px * t, blob_px=blob_px) for b in range(batch)]
         f["meta"]["pre_fetched"] = {"depth": torch.from_numpy(np.stack([v[0].astype(np.int32) for v in views])),
                                     "mask": torch.from_numpy(np.stack([v[1] for v in views]))}
         f["meta"]["path"] = [f"synthetic/1/inst{seed + b}/track0/{t:04d}.npz" for b in range(batch)]
@@ -350,6 +352,22 @@ def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float =
             p["translation"] = torch.from_numpy(np.stack([v[3]["translation"] for v in views])).float()
             p["scale"] = torch.tensor([float(v[3]["scale"]) for v in views])
     return data
+
+
+def cat_trajectories(parts):
+    """Single-trajectory frame lists (make_otf_trajectory(1, ...)) concatenated along the batch axis: a batch whose trajectories are
+    copies of a few seeded ones costs the host those few trajectories' depth images, not the batch's."""
+    out = []
+    for frames in zip(*parts):
+        f0 = frames[0]
+        meta = {"path": sum([f["meta"]["path"] for f in frames], []), "ori_path": sum([f["meta"]["ori_path"] for f in frames], []),
+                "points_mean": torch.cat([f["meta"]["points_mean"] for f in frames]), "nocs_corners": torch.cat([f["meta"]["nocs_corners"] for f in frames]),
+                "pre_fetched": {k: torch.cat([f["meta"]["pre_fetched"][k] for f in frames]) for k in ("depth", "mask")},
+                "nocs2camera": [{k: torch.cat([f["meta"]["nocs2camera"][p][k] for f in frames]) for k in ("rotation", "translation", "scale")}
+                                for p in range(len(f0["meta"]["nocs2camera"]))]}
+        out.append({"points": torch.cat([f["points"] for f in frames]), "labels": torch.cat([f["labels"] for f in frames]),
+                    "nocs": torch.cat([f["nocs"] for f in frames]), "meta": meta})
+    return out
 
 
 def _shift2d(a: np.ndarray, dr: int, dc: int) -> np.ndarray:

@@ -507,6 +507,35 @@ int captra_otf_candidates(int b, int cap, int stride, int num_points, const doub
 int captra_otf_finish(int b, int cap, int stride, int n, const double *pts, const unsigned char *obj, const int *counts,
                       const int *picks, const float *mean, const double *rot, const double *trans, const double *scale,
                       float *points_cn, long long *labels, float *nocs_cn, captra_stream_t stream);
+/* Thinning of over-long candidate lists ON THE DEVICE (csrc/otf_thin.hip), opt-in: with it a crop of more than T = 5 num_points ball
+ * members is no rare-path instance of the two calls above.  Instance i is thinned iff T < c <= cap, c = counts[2 i]; its row of
+ * table (B, T) int32 then receives T member numbers and thinned[i] = 1.  Every other row of table is left untouched (not a byte is
+ * written) and its thinned[i] = 0.
+ * Keys, in 64-bit integer arithmetic with wrap-around, mix = splitmix64's finaliser as for captra_part_fit_ransac:
+ *     key  = mix(seed + 0x9E3779B97F4A7C15)
+ *     row  = mix(key ^ ((uint64)(b0 + i) << 32 | frame))
+ *     u(j) = mix(row ^ (uint64)j) >> 32          (32 bits), j = member number in [0, c)
+ * keys (B, cap) uint32, when not NULL: u(j) = keys[i][j] as it is (the hook for ties and extremes, like sample_rank of the fits).
+ * Selected: the T members with the smallest (u(j), j) in lexicographic order -- a uniformly random T-subset, ties at the threshold
+ * going to the lower member number --, written in ASCENDING member number, i.e. row-major pixel order.
+ * A DELIBERATE DEPARTURE FROM THE REFERENCE: its thinned list is a prefix of numpy.random.permutation (nocs_data_process.py:92-109,
+ * data_utils.py:138-157), so it is in permuted order and its sampler starts from a random member; here the sampler starts from the
+ * first selected member in pixel order, as it does for every unthinned list.  The subset is a pure function of (seed, b0 + i, frame,
+ * c): a lane launched with its b0 draws what the whole batch draws, a replayed frame what its first run drew.
+ * Returns -1 without a launch for b < 0, cap < 1, num_points < 1, b0 < 0, b0 > INT_MAX - b or 5 num_points beyond an int; b = 0: 0. */
+int captra_otf_thin(int b, int cap, int num_points, int b0, unsigned frame, unsigned long long seed, const int *counts,
+                    const unsigned *keys, int *table, int *thinned, captra_stream_t stream);
+/* captra_otf_candidates / captra_otf_finish reading captra_otf_thin's table (B, 5 num_points) and thinned (B,) (for captra_otf_finish_thin
+ * n IS num_points: the table's rows are 5 n long).  A row with thinned[i] != 0: candidate j = member table[i][j], length T = 5 num_points,
+ * a pick p maps to member table[i][p] instead of p modulo the count.  Such a row is rare only when T > stride (a bound outgrown: its
+ * list is the table's first `stride` entries, so every access stays inside its buffers); info[1] takes T for it, info[2] = the number
+ * of thinned rows of the launch.  c < 10 and c > cap stay rare.  With thinned all zero: the plain calls' outputs, bit for bit. */
+int captra_otf_candidates_thin(int b, int cap, int stride, int num_points, const double *pts, const int *counts, float *cand, int *lens,
+                               int *info, const int *table, const int *thinned, captra_stream_t stream);
+int captra_otf_finish_thin(int b, int cap, int stride, int n, const double *pts, const unsigned char *obj, const int *counts,
+                           const int *picks, const float *mean, const double *rot, const double *trans, const double *scale,
+                           float *points_cn, long long *labels, float *nocs_cn, const int *table, const int *thinned,
+                           captra_stream_t stream);
 
 /* Ragged batch of the same operation: the clouds are padded to n_stride points each (xyz (B,n_stride,3)) and cloud i
  * samples m of its FIRST n_per_cloud[i] points (device array of B ints, 1 <= n_per_cloud[i] <= n_stride; NULL = all
