@@ -93,6 +93,7 @@ _SIGNATURES = {
     "captra_otf_thin": [_INT, _INT, _INT, _INT, C.c_uint, C.c_ulonglong, _P, _P, _P, _P, _P],
     "captra_otf_candidates_thin": [_INT, _INT, _INT, _INT, _P, _P, _P, _P, _P, _P, _P, _P],
     "captra_otf_finish_thin": [_INT, _INT, _INT, _INT] + [_P] * 13 + [_P],
+    "captra_depth_support_filter": [_INT] * 7 + [_P, _P, _P, _P],
     "captra_sa_scale_pre": [_INT] * 8 + [_P] * 9 + [_P, _INT, _INT, _P],
     "captra_sa_scale_pre_pm": [_INT] * 8 + [_P] * 9 + [_P, _INT, _INT, _P],
     "captra_pointwise_mlp_pm": [_INT, _INT, _INT, _LL, _P, _P, _P, _INT, _P, _P],

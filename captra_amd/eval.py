@@ -138,6 +138,15 @@ def otf_thin_table(name: str, data: dict) -> list:
     return [f"{name}: thinned {sum(1 for _, t in frames if t != 0)} / {len(frames)} frames"]
 
 
+def depth_filter_table(name: str, data: dict) -> list:
+    """The depth filter's record of one result pickle (present when the run had track_cfg/depth_filter): one line with the pixels
+    the filter set to 0 in the trajectory's depth images -- their sum, mean and maximum over the frames that had a depth image."""
+    counts = [int(np.asarray(r["removed"]).reshape(-1)[0]) for r in data["depth_filter"] if r is not None and "removed" in r]
+    if not counts:
+        return [f"{name}: removed 0 pixels in 0 frames"]
+    return [f"{name}: removed {sum(counts)} pixels in {len(counts)} frames (mean {np.mean(counts):.1f}, max {max(counts)} per frame)"]
+
+
 def write_csv(errors: dict, path: str) -> None:
     keys = list(next(iter(errors.values())).keys())
     with open(path, "w") as f:
@@ -163,7 +172,7 @@ def main(argv=None) -> dict:
     del args.eval_device
     cfg = get_config(args, save=False)
     data_path = pjoin(cfg["experiment_dir"], "results", "data")
-    errors, guard_lines, guard_tests, st_lines, rot_lines, thin_lines = {}, [], set(), [], [], []
+    errors, guard_lines, guard_tests, st_lines, rot_lines, thin_lines, depth_lines = {}, [], set(), [], [], [], []
     for raw in sorted(os.listdir(data_path)):
         with open(pjoin(data_path, raw), "rb") as f:
             data = pickle.load(f)
@@ -177,6 +186,8 @@ def main(argv=None) -> dict:
             rot_lines += rot_pool_table(raw.rsplit(".", 1)[0], data)
         if "otf_thin" in data:
             thin_lines += otf_thin_table(raw.rsplit(".", 1)[0], data)
+        if "depth_filter" in data:
+            depth_lines += depth_filter_table(raw.rsplit(".", 1)[0], data)
     if not errors:
         raise SystemExit(f"no result pickles under {data_path}")
     err_path = pjoin(cfg["experiment_dir"], "results", "err.pkl")
@@ -201,6 +212,10 @@ def main(argv=None) -> dict:
     if thin_lines:
         print("re-crop lists thinned on the device (track_cfg/otf_thin), frames per trajectory:")
         for line in thin_lines:
+            print("  " + line)
+    if depth_lines:
+        print("flying depth pixels removed at upload (track_cfg/depth_filter), per trajectory:")
+        for line in depth_lines:
             print("  " + line)
     return avg
 

@@ -159,6 +159,13 @@ class EvalTrackModel(BaseModel):
         # is launched, no tensor, no pickle entry, numpy's generator is consumed as before.
         self.otf_thin = self._otf_thin_cfg(cfg)
         self._otf_thin_rec = {}             # frame -> {first trajectory of a slice: its thinned flags (b,) int32 on the device}
+        # track_cfg: {depth_filter: {window: 2, abs_mm: <int>, rel_permille: 0, min_support: <int>}}: every uploaded depth image loses
+        # its flying pixels -- those that fewer than min_support of their image neighbours support in depth (csrc/depth_filter.hip,
+        # include/captra_hip.h: captra_depth_support_filter) -- ONCE, when the frame is put on the device (set_data): one launch per
+        # frame over all trajectories, outside the step, the lanes and the replay of a flagged frame, which all read the filtered
+        # image.  The removed pixels are recorded per frame and trajectory (pred_dict / pickle 'depth_filter').  Absent: nothing is
+        # launched, no tensor, no pickle entry, the upload is used as it is.
+        self.depth_filter = self._depth_filter_cfg(cfg)
         self.radius = cfg["data_radius"]
         self.det_category = cfg["obj_category"]          # nocs2d_label: the class id the frame's detections are matched against
         self._det_missing_logged = False
@@ -253,6 +260,25 @@ class EvalTrackModel(BaseModel):
         return {"seed": seed}
 
     @staticmethod
+    def _depth_filter_cfg(cfg):
+        """track_cfg/depth_filter, parsed once: None when absent, else {'window', 'abs_mm', 'rel_permille', 'min_support'} inside the
+        kernel's ranges.  abs_mm and min_support have no default: the right values depend on the sensor and on the window."""
+        from .nocs_otf import check_depth_filter_params
+        f = cfg["track_cfg"].get("depth_filter")
+        if f is None:
+            return None
+        if not cfg.get("nocs_otf", False):
+            raise ValueError("track_cfg/depth_filter filters the depth images the on-the-fly re-crop reads: it needs nocs_otf: True "
+                             "(without it there is no depth image)")
+        for key in ("abs_mm", "min_support"):
+            if f.get(key) is None:
+                raise ValueError(f"track_cfg/depth_filter needs track_cfg/depth_filter/{key}: it has no default")
+        window, rel = f.get("window"), f.get("rel_permille")
+        vals = check_depth_filter_params(2 if window is None else window, f["abs_mm"], 0 if rel is None else rel, f["min_support"],
+                                         prefix="track_cfg/depth_filter/")
+        return dict(zip(("window", "abs_mm", "rel_permille", "min_support"), vals))
+
+    @staticmethod
     def _rot_pool_cfg(cfg):
         """track_cfg/rot_pool, parsed once: None when absent or consensus is not set; angle_th (degrees) has no default -- the right
         value depends on the trained network's vote scatter --, num_hyps and seed default to init_frame's, as st_fit's do."""
@@ -314,6 +340,11 @@ class EvalTrackModel(BaseModel):
         if pre is not None:      # nocs_otf: the frame's depth image and instance mask live on the device
             out["pre_fetched"] = {"depth": torch.as_tensor(pre["depth"]).to(self.device).int(),
                                   "mask": torch.as_tensor(pre["mask"]).to(self.device).bool()}
+            if self.depth_filter is not None:
+                # flying pixels out of the uploaded image, all trajectories in one launch; the counts stay on the device
+                from .nocs_otf import depth_support_filter
+                out["pre_fetched"]["depth"], out["depth_filter_removed"] = depth_support_filter(out["pre_fetched"]["depth"].contiguous(),
+                                                                                                **self.depth_filter)
             if self.track_cfg["nocs2d_label"] and all(k in pre for k in DET_KEYS):
                 # the frame's 2D detections (boxes, classes, count, masks): the re-crop selects among them on the device
                 out["pre_fetched"].update({k: torch.as_tensor(pre[k]).to(self.device).to(torch.uint8 if k == "det_masks" else torch.int32).contiguous()
@@ -893,6 +924,9 @@ class EvalTrackModel(BaseModel):
             rec = self._otf_thin_rec
             self.pred_dict["otf_thin"] = [None] + [next(iter(rec[i].values())) if len(rec[i]) == 1 else torch.cat([rec[i][k] for k in sorted(rec[i])])
                                                    for i in range(1, len(feed))]
+        if self.depth_filter is not None:
+            # per frame: the pixels the filter set to 0 in every trajectory's image, (B,) int32 (None: a frame without depth)
+            self.pred_dict["depth_filter"] = [f.get("depth_filter_removed") for f in feed]
         self.check_l1_stream()
         if save:
             self._save(list(map(_frame_names, feed)))
@@ -944,6 +978,8 @@ class EvalTrackModel(BaseModel):
             save_dict["rot_pool"] = [None if r is None else {k: v.detach().cpu().numpy() for k, v in r.items()} for r in self.pred_dict["rot_pool"]]
         if "otf_thin" in self.pred_dict:
             save_dict["otf_thin"] = [None if r is None else {"thinned": r.detach().cpu().numpy()} for r in self.pred_dict["otf_thin"]]
+        if "depth_filter" in self.pred_dict:
+            save_dict["depth_filter"] = [None if r is None else {"removed": r.detach().cpu().numpy()} for r in self.pred_dict["depth_filter"]]
         records = []
         for i, path in enumerate(self.feed_dict[0]["meta"]["path"]):
             instance, track_num = path.split(".")[-2].split("/")[-3:-1]

@@ -254,6 +254,45 @@ def _arange(n: int, dev) -> torch.Tensor:
 DET_KEYS = ("det_boxes", "det_class", "det_count", "det_masks")
 
 
+def check_depth_filter_params(window, abs_mm, rel_permille, min_support, prefix: str = "") -> tuple:
+    """The four parameters of captra_depth_support_filter as ints, or a ValueError that names the one outside the kernel's range
+    (`prefix`: where the caller read them, e.g. 'track_cfg/depth_filter/')."""
+    vals = {}
+    for key, v in (("window", window), ("abs_mm", abs_mm), ("rel_permille", rel_permille), ("min_support", min_support)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{prefix}{key} must be an integer, got {v!r}")
+        vals[key] = int(v)
+    if vals["window"] not in (1, 2, 3):
+        raise ValueError(f"{prefix}window must be 1, 2 or 3 (a square of 3, 5 or 7 pixels), got {vals['window']}")
+    if not 0 <= vals["abs_mm"] <= 2 ** 31 - 1:
+        raise ValueError(f"{prefix}abs_mm (millimetres) must be in [0, 2^31 - 1], got {vals['abs_mm']}")
+    if not 0 <= vals["rel_permille"] <= 1000:
+        raise ValueError(f"{prefix}rel_permille must be in [0, 1000], got {vals['rel_permille']}")
+    most = (2 * vals["window"] + 1) ** 2 - 1
+    if not 1 <= vals["min_support"] <= most:
+        raise ValueError(f"{prefix}min_support must be in [1, {most}] (the other pixels of a window of {vals['window']}), got {vals['min_support']}")
+    return vals["window"], vals["abs_mm"], vals["rel_permille"], vals["min_support"]
+
+
+def depth_support_filter(depth: torch.Tensor, window: int, abs_mm: int, rel_permille: int, min_support: int):
+    """Flying-pixel rejection on depth images (include/captra_hip.h: captra_depth_support_filter, where the rule is stated): a pixel
+    with depth d > 0 is kept when at least `min_support` of the other in-image pixels of the (2 window + 1)^2 square around it have a
+    depth within abs_mm + floor(d rel_permille / 1000) millimetres of d, else set to 0; pixels with d <= 0 pass through.
+    depth: (B,H,W) or (H,W) int32 on the device, contiguous.  -> (filtered depth, a new tensor of depth's shape; removed: int32 (B,)
+    on the device, the pixels of each image set to 0 -- for an (H,W) image a 0-dim tensor).  One launch, nothing visits the host."""
+    from . import _lib as L
+    L.require_device(depth)
+    if depth.dtype != torch.int32 or depth.dim() not in (2, 3):
+        raise ValueError(f"depth_support_filter takes an int32 tensor (B,H,W) or (H,W), got {depth.dtype} {tuple(depth.shape)}")
+    window, abs_mm, rel_permille, min_support = check_depth_filter_params(window, abs_mm, rel_permille, min_support)
+    B, H, W = (1, *depth.shape) if depth.dim() == 2 else depth.shape
+    out = torch.empty_like(depth)
+    removed = torch.zeros(B, dtype=torch.int32, device=depth.device)
+    with torch.cuda.device(depth.device):
+        L.call("captra_depth_support_filter", B, H, W, window, abs_mm, rel_permille, min_support, L.ptr(depth), L.ptr(out), L.ptr(removed))
+    return out, (removed.reshape(()) if depth.dim() == 2 else removed)
+
+
 def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, intrinsics=NOCS_REAL_INTRINSICS, stacked: bool = True,
                            pose_dev=None, gt_dev=None, defer=None, mean=None, det=None, thin=None):
     """full_data_batch on already-stacked inputs (the track loop's form: no per-trajectory Python on the frame's critical

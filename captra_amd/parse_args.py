@@ -38,6 +38,10 @@ _FLAGS = [  # (name, type, default)
     ("track_cfg/rot_pool/num_hyps", int, None), ("track_cfg/rot_pool/seed", int, None),
     # the re-crop's over-long candidate lists thinned on the device (model.py: EvalTrackModel.otf_thin); off unless device is True
     ("track_cfg/otf_thin/device", boolean_string, None), ("track_cfg/otf_thin/seed", int, None),
+    # flying depth pixels removed from every uploaded depth image (model.py: EvalTrackModel.depth_filter); on when any of the four is
+    # given, and then abs_mm (millimetres) and min_support are required
+    ("track_cfg/depth_filter/window", int, None), ("track_cfg/depth_filter/abs_mm", int, None),
+    ("track_cfg/depth_filter/rel_permille", int, None), ("track_cfg/depth_filter/min_support", int, None),
     # optimisation
     ("total_epoch", int, None), ("optimizer", str, None), ("weight_decay", float, None), ("learning_rate", float, None),
     ("lr_policy", str, None), ("lr_gamma", float, None), ("lr_step_size", int, None), ("lr_clip", float, None), ("freq/save", int, None),

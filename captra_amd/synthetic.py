@@ -168,11 +168,21 @@ PHYSICAL_SETUPS_MORE = {
 }
 
 # ---- depth frames (the on-the-fly re-crop's input) -----------------------------------------------------------------------
-def make_frame(seed: int, height: int = 480, width: int = 640, dr: float = 0.0, dc: float = 0.0, blob_px: float = 70):
+FLYING_STREAM = 0xF1E1          # make_frame's flying pixels: the first word of their generator's seed sequence
+
+
+def make_frame(seed: int, height: int = 480, width: int = 640, dr: float = 0.0, dc: float = 0.0, blob_px: float = 70, flying: float = 0.0,
+               return_flying: bool = False):
     """Synthetic depth frame (uint16 mm) with an object blob in front of a wavy background, its mask, a predicted centre
     and radius, and an instance pose.  (dr, dc): the blob displaced by that many pixel rows / columns -- a moving object over
     the frames of a trajectory; the defaults are golden G11's frames.  blob_px: the blob's radius in pixels (70: about 15 100 ball
-    members at the tracking radius; 90: a close-up of about 24 950, more than the 5 x 4096 an unthinned candidate list holds)."""
+    members at the tracking radius; 90: a close-up of about 24 950, more than the 5 x 4096 an unthinned candidate list holds).
+    flying > 0: the defect of a structured-light or time-of-flight sensor along a silhouette -- every depth-carrying pixel within 1.5
+    pixels of the blob's outline gets, independently with probability `flying`, a depth drawn uniformly from 975..1130 mm, between
+    the blob (900..940 at blob_px 70, up to 953 at its rim at blob_px 90) and the background (about 1360..1640) and more than 20 mm
+    from either, so that no genuine pixel supports a flying one at a tolerance of up to 20 mm.  Drawn from a generator of its own,
+    seeded from `seed`: the frame's own stream does not move, and flying = 0.0 is the frame as it always was.  return_flying: the
+    mask of the injected pixels as a fifth result."""
     rng = np.random.default_rng(seed)
     r, c = np.mgrid[0:height, 0:width]
     depth = 1500.0 + 80.0 * np.sin(r / 37.0) + 60.0 * np.cos(c / 53.0)
@@ -182,6 +192,11 @@ def make_frame(seed: int, height: int = 480, width: int = 640, dr: float = 0.0, 
     depth[blob] = 900.0 + 0.004 * rr[blob] ** 2 + 20.0 * np.sin(c[blob] / 9.0)
     depth[rng.random(depth.shape) < 0.02] = 0.0                       # holes
     depth = depth.astype(np.uint16)
+    injected = np.zeros(depth.shape, bool)
+    if flying > 0.0:
+        fly_rng = np.random.default_rng([FLYING_STREAM, seed])
+        injected = (np.abs(rr - blob_px) <= 1.5) & (depth > 0) & (fly_rng.random(depth.shape) < flying)
+        depth[injected] = fly_rng.integers(975, 1131, size=depth.shape)[injected].astype(np.uint16)
     mask = blob & (rng.random(depth.shape) < 0.97)
     K = np.array([[591.0125, 0, 322.525], [0, 590.16775, 244.11084], [0, 0, 1]])
     z = 0.95
@@ -189,6 +204,8 @@ def make_frame(seed: int, height: int = 480, width: int = 640, dr: float = 0.0, 
     th = 0.4
     pose = {"rotation": np.array([[np.cos(th), 0, np.sin(th)], [0, 1, 0], [-np.sin(th), 0, np.cos(th)]]),
             "translation": center.reshape(3, 1) + 0.005, "scale": np.float64(0.31)}
+    if return_flying:
+        return depth, mask, center, pose, injected
     return depth, mask, center, pose
 
 
@@ -333,18 +350,21 @@ def make_physical_state_dict(shapes: dict, seed: int, num_parts: int, sym: bool,
     return sd
 
 
-def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float = 6.0, blob_px: float = 70):
+def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float = 6.0, blob_px: float = 70, flying: float = 0.0):
     """A trajectory for the on-the-fly re-crop loop (`nocs_otf=True`, reference model.py:425-452): the frame dicts of
     make_trajectory('nocs', ...) carrying, per frame, the depth image / instance mask the loop re-crops
     (meta['pre_fetched']) and the blob's ground-truth pose (meta['nocs2camera']); trajectory b watches depth frame
     make_frame(seed + b) whose blob drifts by `step_px` pixels per time step.  Also the reference's path conventions
     (meta['path'] = .../<category>/<instance>/<track>/<frame>.npz, meta['ori_path']).  blob_px: make_frame's (90 = the close-up whose
-    candidate lists are thinned)."""
+    candidate lists are thinned).  flying: make_frame's (> 0: flying pixels along the silhouette, their mask (B,H,W) bool in
+    meta['pre_fetched']['flying'])."""
     data = make_trajectory("nocs", batch, frames, seed=seed)
     for t, f in enumerate(data):
-        views = [make_frame(seed + b, dr=0.5 * step_px * t, dc=step_px * t, blob_px=blob_px) for b in range(batch)]
+        views = [make_frame(seed + b, dr=0.5 * step_px * t, dc=step_px * t, blob_px=blob_px, flying=flying, return_flying=True) for b in range(batch)]
         f["meta"]["pre_fetched"] = {"depth": torch.from_numpy(np.stack([v[0].astype(np.int32) for v in views])),
                                     "mask": torch.from_numpy(np.stack([v[1] for v in views]))}
+        if flying > 0.0:
+            f["meta"]["pre_fetched"]["flying"] = torch.from_numpy(np.stack([v[4] for v in views]))
         f["meta"]["path"] = [f"synthetic/1/inst{seed + b}/track0/{t:04d}.npz" for b in range(batch)]
         f["meta"]["ori_path"] = [f"synthetic/scene_{seed + b}/{t:04d}_depth.png" for b in range(batch)]
         for p in f["meta"]["nocs2camera"]:

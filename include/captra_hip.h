@@ -536,6 +536,23 @@ int captra_otf_finish_thin(int b, int cap, int stride, int n, const double *pts,
                            const int *picks, const float *mean, const double *rot, const double *trans, const double *scale,
                            float *points_cn, long long *labels, float *nocs_cn, const int *table, const int *thinned,
                            captra_stream_t stream);
+/* Flying-pixel rejection on the depth images themselves (csrc/depth_filter.hip), in front of everything above: a pixel that too few
+ * of its image neighbours support in depth is set to 0 ("no depth"), so the crop never back-projects it.  depth_in, depth_out
+ * (b, h, w) int32 (millimetres), removed (b,) int32.  The rule, in integer arithmetic throughout:
+ *   - a pixel with d > 0 has tol = abs_mm + (d * rel_permille) / 1000, the product and the sum in 64-bit, the division floored;
+ *   - its neighbours are the OTHER pixels of the (2 window + 1)^2 square around it that lie inside its own image: the pixel itself
+ *     is none, nothing wraps around a row end or an image end, nothing is read from the next image of the batch;
+ *   - a neighbour with depth d' supports it when d' > 0 and |d' - d| <= tol, the difference in 64-bit;
+ *   - with at least min_support supporters depth_out = d, else depth_out = 0;
+ *   - a pixel with d <= 0 is copied unchanged (it counts as removed nowhere, and supports nobody);
+ *   - removed[i] is INCREASED by the number of pixels of image i that were set to 0: the caller zeroes it.
+ * Every decision is taken from depth_in, in one pass; depth_out must not overlap depth_in.  The result does not depend on the launch
+ * geometry; the count is accumulated with integer atomics.
+ * Returns -1 without a launch (depth_out and removed untouched) for b, h or w < 0, window outside {1, 2, 3}, abs_mm < 0, rel_permille
+ * outside [0, 1000], min_support outside [1, (2 window + 1)^2 - 1], h or w above INT_MAX - 128, overlapping images, a NULL pointer
+ * with pixels to filter, or more than INT_MAX tiles of 16 x 64 pixels; b, h or w = 0: 0, nothing to do. */
+int captra_depth_support_filter(int b, int h, int w, int window, int abs_mm, int rel_permille, int min_support, const int *depth_in,
+                                int *depth_out, int *removed, captra_stream_t stream);
 
 /* Ragged batch of the same operation: the clouds are padded to n_stride points each (xyz (B,n_stride,3)) and cloud i
  * samples m of its FIRST n_per_cloud[i] points (device array of B ints, 1 <= n_per_cloud[i] <= n_stride; NULL = all
