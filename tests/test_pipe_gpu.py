@@ -12,6 +12,26 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("xyz_feat,depth", [(False, 2), (True, 3)])
 def test_backbone_pipe_equals_plain_forward(device, xyz_feat, depth):
+    _pipe_equals_plain_forward(device, xyz_feat, depth, B=3, T=7)
+
+
+@pytest.mark.parametrize("route", ["static_walks", "reserve_all_but_32"])
+def test_backbone_pipe_on_a_smaller_grid_equals_plain_forward(device, monkeypatch, route):
+    """The two other ways the pipeline sizes its persistent SA kernels (graph.py:325-355): CAPTRA_PIPE_DYNAMIC=0 -- static centre
+    walks with one CU reserved per cloud -- and the dynamic hand-out on a grid of 32 CUs (`reserve`, captra_launch_opts::reserved_cus)."""
+    monkeypatch.delenv("CAPTRA_PIPE_RESERVE", raising=False)
+    if route == "static_walks":
+        monkeypatch.setenv("CAPTRA_PIPE_DYNAMIC", "0")
+        pipe = _pipe_equals_plain_forward(device, False, 2, B=2, T=4)
+        assert not pipe.dynamic and pipe.reserve == 2
+    else:
+        monkeypatch.delenv("CAPTRA_PIPE_DYNAMIC", raising=False)
+        cus = torch.cuda.get_device_properties(device).multi_processor_count
+        pipe = _pipe_equals_plain_forward(device, False, 2, B=2, T=4, reserve=cus - 32)
+        assert pipe.dynamic and pipe.reserve == cus - 32
+
+
+def _pipe_equals_plain_forward(device, xyz_feat, depth, B, T, reserve=None):
     from captra_amd import synthetic as clouds
     from captra_amd.backbones import PointNet2Msg
     from captra_amd.configs import make_config
@@ -21,12 +41,11 @@ def test_backbone_pipe_equals_plain_forward(device, xyz_feat, depth):
     net = PointNet2Msg(cfg, 128, use_xyz_feat=xyz_feat)
     net.load_state_dict(make_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, seed=5))
     net = net.to(device).eval()
-    B, N, T = 3, 4096, 7
     xs = [torch.from_numpy(np.ascontiguousarray(np.stack([clouds.s_nocs(100 * t + i)[0] for i in range(B)]).transpose(0, 2, 1))).to(device)
           for t in range(T)]
     with torch.no_grad():
         want = [net(x).clone() for x in xs]
-    pipe = BackbonePipe(net, xs[0], depth=depth)
+    pipe = BackbonePipe(net, xs[0], depth=depth, reserve=reserve)
     got = []
     # outputs are read `depth - 1` pushes late, as a consumer of the pipeline would
     slots = []
@@ -45,6 +64,7 @@ def test_backbone_pipe_equals_plain_forward(device, xyz_feat, depth):
     assert torch.equal(pipe.output(s), want[T - depth])
     pipe.drain()
     torch.cuda.synchronize()
+    return pipe
 
 
 def test_backbone_pipe_rejects_training_mode(device):
