@@ -94,6 +94,7 @@ _SIGNATURES = {
     "captra_otf_candidates_thin": [_INT, _INT, _INT, _INT, _P, _P, _P, _P, _P, _P, _P, _P],
     "captra_otf_finish_thin": [_INT, _INT, _INT, _INT] + [_P] * 13 + [_P],
     "captra_depth_support_filter": [_INT] * 7 + [_P, _P, _P, _P],
+    "captra_image_members": [_INT] * 6 + [_P] * 9 + [_P],
     "captra_sa_scale_pre": [_INT] * 8 + [_P] * 9 + [_P, _INT, _INT, _P],
     "captra_sa_scale_pre_pm": [_INT] * 8 + [_P] * 9 + [_P, _INT, _INT, _P],
     "captra_pointwise_mlp_pm": [_INT, _INT, _INT, _LL, _P, _P, _P, _INT, _P, _P],
@@ -145,6 +146,7 @@ _AUX_SIGNATURES = {
     "captra_sa1_stream_set_fine": ([_INT], None),
     "captra_sa1_stream_set_whole": ([_INT], None),
     "captra_neck_chain_set_split": ([_INT], None),
+    "captra_image_members_set_split": ([_INT], None),
     "captra_query_and_group_set_shape": ([_INT, _INT], None),
     "captra_pointwise_mlp_gn_tiles": ([_INT, _INT, _LL], _INT),
     "captra_pointwise_mlp_gn_tiles_ex": ([_INT, _INT, _LL, _P], _INT),

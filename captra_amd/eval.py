@@ -147,6 +147,13 @@ def depth_filter_table(name: str, data: dict) -> list:
     return [f"{name}: removed {sum(counts)} pixels in {len(counts)} frames (mean {np.mean(counts):.1f}, max {max(counts)} per frame)"]
 
 
+def image_fit_table(name: str, data: dict) -> list:
+    """The first-pose image fit's record of one result pickle (present when the run had init_frame/image_fit): one line with the
+    members the eroded mask held, those the fit used, the holes, the inliers of the fit and whether it was valid."""
+    r = {k: int(np.asarray(v).reshape(-1)[0]) for k, v in data["image_fit"].items()}
+    return [f"{name}: members {r['members']}; used {r['used']}; holes {r['holes']}; inliers {r['inliers']}; valid {'yes' if r['valid'] else 'no'}"]
+
+
 def write_csv(errors: dict, path: str) -> None:
     keys = list(next(iter(errors.values())).keys())
     with open(path, "w") as f:
@@ -172,7 +179,7 @@ def main(argv=None) -> dict:
     del args.eval_device
     cfg = get_config(args, save=False)
     data_path = pjoin(cfg["experiment_dir"], "results", "data")
-    errors, guard_lines, guard_tests, st_lines, rot_lines, thin_lines, depth_lines = {}, [], set(), [], [], [], []
+    errors, guard_lines, guard_tests, st_lines, rot_lines, thin_lines, depth_lines, image_lines = {}, [], set(), [], [], [], [], []
     for raw in sorted(os.listdir(data_path)):
         with open(pjoin(data_path, raw), "rb") as f:
             data = pickle.load(f)
@@ -188,6 +195,8 @@ def main(argv=None) -> dict:
             thin_lines += otf_thin_table(raw.rsplit(".", 1)[0], data)
         if "depth_filter" in data:
             depth_lines += depth_filter_table(raw.rsplit(".", 1)[0], data)
+        if "image_fit" in data:
+            image_lines += image_fit_table(raw.rsplit(".", 1)[0], data)
     if not errors:
         raise SystemExit(f"no result pickles under {data_path}")
     err_path = pjoin(cfg["experiment_dir"], "results", "err.pkl")
@@ -216,6 +225,10 @@ def main(argv=None) -> dict:
     if depth_lines:
         print("flying depth pixels removed at upload (track_cfg/depth_filter), per trajectory:")
         for line in depth_lines:
+            print("  " + line)
+    if image_lines:
+        print("first pose fitted from frame 0's images (init_frame/image_fit), per trajectory:")
+        for line in image_lines:
             print("  " + line)
     return avg
 

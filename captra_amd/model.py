@@ -135,6 +135,12 @@ class EvalTrackModel(BaseModel):
         # captra_part_fit_guard_sym) for a symmetric category, whose tracked in-plane angle carries no information.  Absent / False:
         # today's launches and records; True on a category that is not symmetric is an error.
         self.fit_init_yaxis = self._yaxis_only(cfg, cfg["init_frame"], "init_frame/yaxis_only")
+        # init_frame: {image_fit: True, border: 0, cap: 16384, coord_negate_z: False}: the first pose is fitted to frame 0's IMAGES -- the
+        # depth image, the instance mask and the NOCS coordinate image of meta['pre_fetched'], the three outputs of a NOCS-style
+        # detector (csrc/image_fit.hip turns them into correspondences, the same RANSAC fit as init_frame/fit reads them with its
+        # inlier_th, num_hyps, seed and yaxis_only) -- so a track starts from images alone.  The fit is recorded (pred_dict / pickle
+        # 'image_fit').  Absent / False: no launch, no tensor, no pickle entry.
+        self.image_fit = self._image_fit_cfg(cfg)
         self._fit_fallback_logged = False
         # track_cfg: {guard: {...}}: every step checks the pose it produced against the frame's own NOCS map, labels and points
         # (csrc/pose_guard.hip, one launch behind the pose fit, captured with the step) and, with refit, re-fits a part found lost
@@ -249,6 +255,23 @@ class EvalTrackModel(BaseModel):
         return {"inlier_th": frac * float(cfg["data_radius"]), "num_hyps": num_hyps, "seed": seed}
 
     @staticmethod
+    def _image_fit_cfg(cfg):
+        """init_frame/image_fit, parsed once: None when absent or not set, else {'cap', 'border', 'negate_z'} inside the kernels' ranges."""
+        from .nocs_otf import IMAGE_FIT_CAP, check_image_fit_params
+        f = cfg["init_frame"]
+        if not f.get("image_fit", False):
+            return None
+        if f.get("fit", False):
+            raise ValueError("init_frame/image_fit and init_frame/fit both fit the first pose, one from frame 0's images and one from its "
+                             "pre-cropped cloud: set one of them")
+        if int(cfg["num_parts"]) != 1:
+            raise ValueError(f"init_frame/image_fit fits one rigid object (a coordinate image describes one), this object has num_parts = "
+                             f"{cfg['num_parts']}")
+        cap, border = f.get("cap"), f.get("border")
+        cap, border = check_image_fit_params(IMAGE_FIT_CAP if cap is None else cap, 0 if border is None else border, prefix="init_frame/")
+        return {"cap": cap, "border": border, "negate_z": bool(f.get("coord_negate_z", False))}
+
+    @staticmethod
     def _otf_thin_cfg(cfg):
         """track_cfg/otf_thin, parsed once: None when absent or device is not set, else {'seed'}."""
         t = cfg["track_cfg"].get("otf_thin")
@@ -312,7 +335,7 @@ class EvalTrackModel(BaseModel):
     def _warn_full_rotation_test(self, cfg):
         """Once per model object: a symmetric category judged by the full-rotation test."""
         uses = [name for name, on, yaxis in (("track_cfg/guard", self.guard is not None, self.guard is not None and self.guard.get("yaxis_only", False)),
-                                             ("init_frame/fit", self.fit_init, self.fit_init_yaxis)) if on and not yaxis]
+                                             ("init_frame/fit", self.fit_init or self.image_fit is not None, self.fit_init_yaxis)) if on and not yaxis]
         if cfg["obj_sym"] and uses:
             logging.getLogger(__name__).warning(
                 "%s on a symmetric category (%s) with the full-rotation inlier test in use: the tracked in-plane angle carries no "
@@ -345,6 +368,8 @@ class EvalTrackModel(BaseModel):
                 from .nocs_otf import depth_support_filter
                 out["pre_fetched"]["depth"], out["depth_filter_removed"] = depth_support_filter(out["pre_fetched"]["depth"].contiguous(),
                                                                                                 **self.depth_filter)
+            if first and self.image_fit is not None and "coord" in pre:
+                out["pre_fetched"]["coord"] = torch.as_tensor(pre["coord"]).to(self.device).to(torch.uint8).contiguous()
             if self.track_cfg["nocs2d_label"] and all(k in pre for k in DET_KEYS):
                 # the frame's 2D detections (boxes, classes, count, masks): the re-crop selects among them on the device
                 out["pre_fetched"].update({k: torch.as_tensor(pre[k]).to(self.device).to(torch.uint8 if k == "det_masks" else torch.int32).contiguous()
@@ -372,6 +397,9 @@ class EvalTrackModel(BaseModel):
     # ---- the loop ------------------------------------------------------------------------------
     def _initial_pose(self):
         part = self._annotated_initial_pose()
+        self._image_fit_rec = None
+        if self.image_fit is not None:
+            return self._image_fitted_initial_pose(part)
         return self._fitted_initial_pose(part) if self.fit_init else part
 
     def _annotated_initial_pose(self):
@@ -403,6 +431,35 @@ class EvalTrackModel(BaseModel):
         if not self._fit_fallback_logged and not bool(valid.all()):
             self._fit_fallback_logged = True
             logging.getLogger(__name__).warning("init_frame/fit: %d of %d first-pose fits are invalid; those parts start from the "
+                                                "annotated pose", int((~valid).sum()), valid.numel())
+        return {"rotation": torch.where(valid[..., None, None], rot, fallback["rotation"]),
+                "scale": torch.where(valid, scale, fallback["scale"]),
+                "translation": torch.where(valid[..., None, None], trans, fallback["translation"])}
+
+    def _image_fitted_initial_pose(self, fallback):
+        """init_frame/image_fit: all B first poses from frame 0's depth image, mask and coordinate image (the depth filter, when
+        configured, has filtered the image in set_data) in two launches -- the correspondences (captra_image_members), the RANSAC
+        fit -- with nothing visiting the host; a fit that is not valid keeps `fallback`.  The record, (B,) int32 each on the device:
+        members, used, holes (the kernel's counts), inliers and valid (the fit's)."""
+        from .nocs_otf import image_members
+        from .pose_utils.pose_fit import part_fit_ransac_cn
+        pre = self.feed_dict[0].get("pre_fetched") or {}
+        missing = [k for k in ("depth", "mask", "coord") if k not in pre]
+        if missing:
+            raise KeyError(f"init_frame/image_fit needs frame 0's {missing} (meta['pre_fetched']: depth image, instance mask, NOCS "
+                           "coordinate image)")
+        cfg = self.image_fit
+        mem = image_members(pre["depth"].contiguous(), pre["mask"].contiguous(), pre["coord"], cap=cfg["cap"], border=cfg["border"],
+                            negate_z=cfg["negate_z"])
+        rot, scale, trans, valid, info = part_fit_ransac_cn(mem["labels"], mem["src"], mem["tgt"], num_hyps=self.fit_init_cfg["num_hyps"],
+                                                            inlier_th=self.fit_init_cfg["inlier_th"], seed=self.fit_init_cfg["seed"],
+                                                            yaxis_only=self.fit_init_yaxis)
+        counts = mem["counts"]
+        self._image_fit_rec = {"members": counts[:, 0].contiguous(), "used": counts[:, 1].contiguous(), "holes": counts[:, 2].contiguous(),
+                               "inliers": info["num_inliers"][:, 0].contiguous(), "valid": valid[:, 0].int()}
+        if not self._fit_fallback_logged and not bool(valid.all()):
+            self._fit_fallback_logged = True
+            logging.getLogger(__name__).warning("init_frame/image_fit: %d of %d first-pose fits are invalid; those parts start from the "
                                                 "annotated pose", int((~valid).sum()), valid.numel())
         return {"rotation": torch.where(valid[..., None, None], rot, fallback["rotation"]),
                 "scale": torch.where(valid, scale, fallback["scale"]),
@@ -927,6 +984,9 @@ class EvalTrackModel(BaseModel):
         if self.depth_filter is not None:
             # per frame: the pixels the filter set to 0 in every trajectory's image, (B,) int32 (None: a frame without depth)
             self.pred_dict["depth_filter"] = [f.get("depth_filter_removed") for f in feed]
+        if self.image_fit is not None:
+            # frame 0's fit: members, used, holes, inliers, valid, (B,) int32 each
+            self.pred_dict["image_fit"] = self._image_fit_rec
         self.check_l1_stream()
         if save:
             self._save(list(map(_frame_names, feed)))
@@ -980,6 +1040,8 @@ class EvalTrackModel(BaseModel):
             save_dict["otf_thin"] = [None if r is None else {"thinned": r.detach().cpu().numpy()} for r in self.pred_dict["otf_thin"]]
         if "depth_filter" in self.pred_dict:
             save_dict["depth_filter"] = [None if r is None else {"removed": r.detach().cpu().numpy()} for r in self.pred_dict["depth_filter"]]
+        if "image_fit" in self.pred_dict:
+            save_dict["image_fit"] = {k: v.detach().cpu().numpy() for k, v in self.pred_dict["image_fit"].items()}
         records = []
         for i, path in enumerate(self.feed_dict[0]["meta"]["path"]):
             instance, track_num = path.split(".")[-2].split("/")[-3:-1]

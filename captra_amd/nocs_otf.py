@@ -293,6 +293,62 @@ def depth_support_filter(depth: torch.Tensor, window: int, abs_mm: int, rel_perm
     return out, (removed.reshape(()) if depth.dim() == 2 else removed)
 
 
+IMAGE_FIT_CAP = 16384           # the most members captra_part_fit_ransac takes
+
+
+def check_image_fit_params(cap, border, prefix: str = "") -> tuple:
+    """cap and border of image_members as ints, or a ValueError that names the one outside its range (`prefix`: where the caller read
+    them, e.g. 'init_frame/')."""
+    vals = {}
+    for key, v in (("cap", cap), ("border", border)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{prefix}{key} must be an integer, got {v!r}")
+        vals[key] = int(v)
+    if not 3 <= vals["cap"] <= IMAGE_FIT_CAP:
+        raise ValueError(f"{prefix}cap must be in [3, {IMAGE_FIT_CAP}] (a fit needs three members, the fit kernel takes {IMAGE_FIT_CAP}), got {vals['cap']}")
+    if not 0 <= vals["border"] <= 3:
+        raise ValueError(f"{prefix}border must be in [0, 3] (pixels eroded from the mask), got {vals['border']}")
+    return vals["cap"], vals["border"]
+
+
+def image_members(depth: torch.Tensor, mask: torch.Tensor, coord: torch.Tensor, intrinsics=NOCS_REAL_INTRINSICS, cap: int = IMAGE_FIT_CAP,
+                  border: int = 0, negate_z: bool = False) -> dict:
+    """The correspondences of a first-pose fit from a frame's images (include/captra_hip.h: captra_image_members, where the rule is
+    stated): the pixels of the instance mask, eroded by `border`, that carry a depth, in row-major order, at most `cap` of them (a
+    fixed stride thins a larger instance), back-projected and paired with the NOCS coordinates the coordinate image encodes.
+    depth (B,H,W) int32 millimetres, mask (B,H,W) bool or uint8, coord (B,H,W,3) uint8 (channel k = NOCS axis k), all on the device
+    and contiguous; (H,W) / (H,W,3) for one image.
+    -> {'src' (B,1,3,cap) fp32, 'tgt' (B,3,cap) fp32 metres, 'labels' (B,cap) int32 (0 = a member, -1 = an empty slot), 'pix' (B,cap)
+    int32, 'counts' (B,3) int32 = members, used, holes}: what part_fit_ransac_cn(labels, src, tgt) reads.  One launch, nothing
+    visits the host."""
+    from . import _lib as L
+    L.require_device(depth, mask, coord)
+    single = depth.dim() == 2
+    if single:
+        depth, mask, coord = depth[None], mask[None], coord[None]
+    if depth.dtype != torch.int32 or depth.dim() != 3:
+        raise ValueError(f"image_members takes the depth as an int32 tensor (B,H,W) or (H,W), got {depth.dtype} {tuple(depth.shape)}")
+    if mask.dtype not in (torch.bool, torch.uint8) or mask.shape != depth.shape:
+        raise ValueError(f"image_members takes the mask as a bool or uint8 tensor of the depth's shape {tuple(depth.shape)}, got {mask.dtype} {tuple(mask.shape)}")
+    if coord.dtype != torch.uint8 or coord.shape != (*depth.shape, 3):
+        raise ValueError(f"image_members takes the coordinate image as a uint8 tensor {(*depth.shape, 3)}, got {coord.dtype} {tuple(coord.shape)}")
+    if not (mask.device == depth.device == coord.device):
+        raise ValueError("image_members takes its three images on one device")
+    cap, border = check_image_fit_params(cap, border)
+    B, H, W = depth.shape
+    dev = depth.device
+    kinv = _intrinsics_on_device(intrinsics, dev)[9:]
+    out = {"src": torch.empty(B, 1, 3, cap, dtype=torch.float32, device=dev), "tgt": torch.empty(B, 3, cap, dtype=torch.float32, device=dev),
+           "labels": torch.empty(B, cap, dtype=torch.int32, device=dev), "pix": torch.empty(B, cap, dtype=torch.int32, device=dev),
+           "counts": torch.zeros(B, 3, dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        L.call("captra_image_members", B, H, W, cap, border, 1 if negate_z else 0, L.ptr(depth), L.ptr(mask.view(torch.uint8)), L.ptr(coord),
+               L.ptr(kinv), L.ptr(out["src"]), L.ptr(out["tgt"]), L.ptr(out["labels"]), L.ptr(out["pix"]), L.ptr(out["counts"]))
+    if H * W == 0:                      # images without a pixel: the call has nothing to do and writes nothing
+        out["src"].zero_(); out["tgt"].zero_(); out["labels"].fill_(-1); out["pix"].fill_(-1)
+    return {k: v[0] for k, v in out.items()} if single else out
+
+
 def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, intrinsics=NOCS_REAL_INTRINSICS, stacked: bool = True,
                            pose_dev=None, gt_dev=None, defer=None, mean=None, det=None, thin=None):
     """full_data_batch on already-stacked inputs (the track loop's form: no per-trajectory Python on the frame's critical

@@ -29,6 +29,10 @@ _FLAGS = [  # (name, type, default)
     # the axis-only inlier test of the symmetric categories, in the guard and in the first-pose fit (init_frame/fit).  Not given = not
     # in the namespace at all (argparse.SUPPRESS): the key reaches the configuration only when it was written
     ("track_cfg/guard/yaxis_only", boolean_string, argparse.SUPPRESS), ("init_frame/yaxis_only", boolean_string, argparse.SUPPRESS),
+    # the first pose fitted from frame 0's depth, mask and NOCS coordinate image (model.py: EvalTrackModel.image_fit); off unless image_fit
+    # is True.  Not given = not in the namespace at all, like yaxis_only
+    ("init_frame/image_fit", boolean_string, argparse.SUPPRESS), ("init_frame/border", int, argparse.SUPPRESS),
+    ("init_frame/cap", int, argparse.SUPPRESS), ("init_frame/coord_negate_z", boolean_string, argparse.SUPPRESS),
     # the robust scale / translation fit of every step (model.py: EvalTrackModel.st_fit); off unless ransac is True
     ("track_cfg/st_fit/ransac", boolean_string, None), ("track_cfg/st_fit/inlier_th", float, None), ("track_cfg/st_fit/num_hyps", int, None),
     ("track_cfg/st_fit/seed", int, None),

@@ -350,14 +350,36 @@ def make_physical_state_dict(shapes: dict, seed: int, num_parts: int, sym: bool,
     return sd
 
 
-def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float = 6.0, blob_px: float = 70, flying: float = 0.0):
+def render_coord_image(depth, mask, pose, intrinsics=None) -> np.ndarray:
+    """The NOCS coordinate image (h,w,3) uint8 of an instance, as a NOCS-style detector or the NOCS dataset delivers it (channel k =
+    NOCS axis k), rendered from the frame's own depth (h,w) and ground-truth pose {'rotation' (3,3), 'translation' (3,1), 'scale'}:
+    every pixel back-projected as the re-crop does (ray = K^-1 (col, h - row, 1); p = ray * z / ray_z; (p_x, p_y, -p_z) * 0.001), NOCS
+    = R^T (p - t) / s, encoded as round((nocs + 0.5) * 255) clipped to [0, 255]; zero off the mask."""
+    K = np.array([[591.0125, 0, 322.525], [0, 590.16775, 244.11084], [0, 0, 1]]) if intrinsics is None else np.asarray(intrinsics, np.float64)
+    h, w = depth.shape
+    r, c = np.mgrid[0:h, 0:w]
+    ray = np.stack([c, h - r, np.ones_like(r)], -1).astype(np.float64) @ np.linalg.inv(K).T
+    p = ray * depth.astype(np.float32).astype(np.float64)[..., None] / ray[..., 2:3]
+    p[..., 2] = -p[..., 2]
+    p *= 0.001
+    R, t, s = np.asarray(pose["rotation"], np.float64), np.asarray(pose["translation"], np.float64).reshape(3), float(pose["scale"])
+    nocs = (p - t) @ R / s
+    img = np.clip(np.round((nocs + 0.5) * 255.0), 0, 255).astype(np.uint8)
+    img[~np.asarray(mask, bool)] = 0
+    return img
+
+
+def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float = 6.0, blob_px: float = 70, flying: float = 0.0,
+                        coord: bool = False):
     """A trajectory for the on-the-fly re-crop loop (`nocs_otf=True`, reference model.py:425-452): the frame dicts of
     make_trajectory('nocs', ...) carrying, per frame, the depth image / instance mask the loop re-crops
     (meta['pre_fetched']) and the blob's ground-truth pose (meta['nocs2camera']); trajectory b watches depth frame
     make_frame(seed + b) whose blob drifts by `step_px` pixels per time step.  Also the reference's path conventions
     (meta['path'] = .../<category>/<instance>/<track>/<frame>.npz, meta['ori_path']).  blob_px: make_frame's (90 = the close-up whose
     candidate lists are thinned).  flying: make_frame's (> 0: flying pixels along the silhouette, their mask (B,H,W) bool in
-    meta['pre_fetched']['flying'])."""
+    meta['pre_fetched']['flying']).  coord: frame 0 also carries meta['pre_fetched']['coord'] (B,h,w,3) uint8, the NOCS coordinate image
+    of the blob rendered from the frame's own depth and ground-truth pose (render_coord_image) -- what `init_frame/image_fit` reads;
+    False: exactly the frames as they always were."""
     data = make_trajectory("nocs", batch, frames, seed=seed)
     for t, f in enumerate(data):
         views = [make_frame(seed + b, dr=0.5 * step_px * t, dc=step_px * t, blob_px=blob_px, flying=flying, return_flying=True) for b in range(batch)]
@@ -365,6 +387,8 @@ def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float =
                                     "mask": torch.from_numpy(np.stack([v[1] for v in views]))}
         if flying > 0.0:
             f["meta"]["pre_fetched"]["flying"] = torch.from_numpy(np.stack([v[4] for v in views]))
+        if coord and t == 0:
+            f["meta"]["pre_fetched"]["coord"] = torch.from_numpy(np.stack([render_coord_image(v[0], v[1], v[3]) for v in views]))
         f["meta"]["path"] = [f"synthetic/1/inst{seed + b}/track0/{t:04d}.npz" for b in range(batch)]
         f["meta"]["ori_path"] = [f"synthetic/scene_{seed + b}/{t:04d}_depth.png" for b in range(batch)]
         for p in f["meta"]["nocs2camera"]:

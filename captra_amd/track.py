@@ -184,8 +184,9 @@ def _load_source(src, args, cfg=None):
             raise SystemExit("--data synthetic needs the repository's tests/ package on sys.path") from e
         _, kind, seed = src
         if otf and kind == "nocs":
-            make = clouds.make_otf_detections if det else clouds.make_otf_trajectory
-            return make(1, args.num_frames, seed=seed)
+            # (init_frame/image_fit: frame 0 also carries its NOCS coordinate image)
+            data = clouds.make_otf_trajectory(1, args.num_frames, seed=seed, coord=bool(cfg["init_frame"].get("image_fit", False)))
+            return clouds.make_otf_detections(1, args.num_frames, seed=seed, data=data) if det else data
         return clouds.make_trajectory(kind, 1, args.num_frames, seed=seed)
     frames = stack_trajectories([load_trajectory_npz(src)])
     if det and cfg["track_cfg"].get("nocs2d_path") and "pre_fetched" in frames[0]["meta"] and "det_boxes" not in frames[0]["meta"]["pre_fetched"]:

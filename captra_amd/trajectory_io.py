@@ -16,6 +16,8 @@ per trajectory -- the arrays a dataset item holds after cropping to N points:
                                (the reference's meta['pre_fetched'], dataset.py:157-194)
     det_boxes (T,K,4) i32 [y1,x1,y2,x2], det_class (T,K) i32, det_count (T,) i32, det_masks (T,K,H,W) u8, optional (with depth / mask):
                                the frames' 2D detections for `--track_cfg/nocs2d_label True`, K slots of which the first det_count hold one
+    coord        (H,W,3) uint8 optional (with depth / mask): FRAME 0's NOCS coordinate image, channel k = NOCS axis k, for
+                               `--init_frame/image_fit True` (the first pose fitted from images alone)
     ori_paths    (T,) str      optional: "…/<scene>/<frame>_depth.png" (meta['ori_path']): names the detector result file of a frame
 
 `stack_trajectories` batches B trajectories of equal length into the (B, …) frame dicts `set_data` takes.
@@ -50,6 +52,8 @@ def save_trajectory_npz(path: str, frames: list, b: int = 0) -> None:
         if all(k in f["meta"]["pre_fetched"] for f in frames for k in DET_KEYS):
             for k in DET_KEYS:
                 out[k] = np.stack([np.asarray(f["meta"]["pre_fetched"][k][b]) for f in frames]).astype(_DET_DTYPES[k])
+        if "coord" in frames[0]["meta"]["pre_fetched"]:
+            out["coord"] = np.asarray(frames[0]["meta"]["pre_fetched"]["coord"][b]).astype(np.uint8)
     if all("ori_path" in f["meta"] for f in frames):
         out["ori_paths"] = np.array([f["meta"]["ori_path"][b] for f in frames])
     np.savez(path, **out)
@@ -61,7 +65,7 @@ def load_trajectory_npz(path: str) -> dict:
         if missing:
             raise ValueError(f"{path}: not a trajectory file, missing {missing}")
         traj = {k: z[k] for k in _KEYS}
-        for k in ("depth", "mask", "ori_paths") + DET_KEYS:
+        for k in ("depth", "mask", "coord", "ori_paths") + DET_KEYS:
             if k in z.files:
                 traj[k] = z[k]
     T = traj["points"].shape[0]
@@ -89,6 +93,8 @@ def stack_trajectories(trajs: list) -> list:
                                    "mask": torch.from_numpy(np.stack([t["mask"][i] for t in trajs]))}
             if all(k in t for t in trajs for k in DET_KEYS):
                 meta["pre_fetched"].update(pad_detections([{k: t[k][i] for k in DET_KEYS} for t in trajs]))
+            if i == 0 and all("coord" in t for t in trajs):
+                meta["pre_fetched"]["coord"] = torch.from_numpy(np.stack([np.asarray(t["coord"], np.uint8) for t in trajs]))
         if all("ori_paths" in t for t in trajs):
             meta["ori_path"] = [str(t["ori_paths"][i]) for t in trajs]
         frames.append({"points": cat("points"), "labels": cat("labels", torch.int64), "nocs": cat("nocs"), "meta": meta})
@@ -118,6 +124,8 @@ def concat_frame_batches(batches: list) -> list:
             meta["pre_fetched"] = {k: torch.cat([torch.as_tensor(f["meta"]["pre_fetched"][k]) for f in frames]) for k in ("depth", "mask")}
             if all(k in f["meta"]["pre_fetched"] for f in frames for k in DET_KEYS):
                 meta["pre_fetched"].update(pad_detections([{k: f["meta"]["pre_fetched"][k] for k in DET_KEYS} for f in frames], batched=True))
+            if all("coord" in f["meta"]["pre_fetched"] for f in frames):
+                meta["pre_fetched"]["coord"] = torch.cat([torch.as_tensor(f["meta"]["pre_fetched"]["coord"]) for f in frames])
         if all("ori_path" in f["meta"] for f in frames):
             meta["ori_path"] = [p for f in frames for p in f["meta"]["ori_path"]]
         out.append({"points": torch.cat([f["points"] for f in frames]), "labels": torch.cat([f["labels"] for f in frames]),

@@ -553,6 +553,35 @@ int captra_otf_finish_thin(int b, int cap, int stride, int n, const double *pts,
  * with pixels to filter, or more than INT_MAX tiles of 16 x 64 pixels; b, h or w = 0: 0, nothing to do. */
 int captra_depth_support_filter(int b, int h, int w, int window, int abs_mm, int rel_permille, int min_support, const int *depth_in,
                                 int *depth_out, int *removed, captra_stream_t stream);
+/* The correspondences of a FIRST-POSE fit from frame 0's images (csrc/image_fit.hip): a depth image, an instance mask and a NOCS
+ * coordinate image -- the three outputs of a NOCS-style detector -- turned into what captra_part_fit_ransac(b, 1, cap, ..., tgt_per_part
+ * = 0, tgt_mean = NULL) reads.  The first half of the reference's get_image_pose (datasets/nocs_data/preproc_nocs/get_gt_poses.py:20-34;
+ * nocs_utils.py:5-33 `backproject`, 44-54 `remove_border`); no pose is needed.
+ *   depth (b,h,w) int32 millimetres; mask (b,h,w) bytes, non-zero = the instance; coord (b,h,w,3) bytes, channel k = NOCS axis k (the
+ *   loader has done the reference's BGR -> RGB reorder, get_gt_poses.py:73); kinv 9 doubles, row-major inverse intrinsics as for
+ *   captra_crop_ball.
+ *   -> src (b,1,3,cap) fp32 channel-major NOCS, tgt (b,3,cap) fp32 camera points in metres, labels (b,cap) int32, pix (b,cap) int32,
+ *      counts (b,3) int32.
+ * The rule; all indexing is integer arithmetic:
+ *   - eroded mask: pixel (r,c) of image i is INSIDE when mask != 0 at every pixel (r',c') with r' in [r - border + 1, r + border] and
+ *     [0,h), c' in [c - border + 1, c + border] and [0,w) -- remove_border's asymmetric window, seen from the pixel that survives;
+ *     border = 0: inside iff mask[r][c] != 0.  Nothing is read from another image of the batch, nothing wraps at a row end.
+ *     A DELIBERATE DEPARTURE FROM THE REFERENCE: it erodes only against background (value 255), not against another instance's
+ *     pixels; here everything outside the instance erodes.  On an image with one instance the two agree.
+ *   - members: the inside pixels with depth > 0, in row-major order; counts[3 i] = their number c.
+ *   - subsampling: c <= cap: every member is used (step = 1); else step = ceil(c / cap) and the members j with j % step == 0 are used,
+ *     j = the member number.  counts[3 i + 1] = used = ceil(c / step) <= cap.  counts[3 i + 2] = the inside pixels with depth <= 0
+ *     (holes are reported, as captra_crop_ball reports its box's depth pixels).
+ *   - slot s < used, holding member j = s step at pixel (r,c): pix = r w + c; labels = 0; tgt = the fp32 rounding of captra_crop_ball's
+ *     float64 back-projection (ray = kinv (c, h - r, 1); p = ray * z / ray_z; (p_x, p_y, -p_z) * 0.001); src_k = fp32(double(coord_k) /
+ *     255.0 - 0.5), src_2 negated when negate_z != 0 (get_gt_poses.py:74-76).
+ *   - slots used <= s < cap: labels = -1, pix = -1, src = tgt = 0: the fit ignores them, no NaN leaves the kernel.
+ * The result does not depend on the launch geometry (integer atomics for the counts, no floating-point atomics).
+ * Returns -1 without a launch and without a byte written for b, h or w < 0, cap < 1, border outside [0, 3], h w beyond an int, or a
+ * NULL pointer while there is work to do; b, h or w = 0: 0, nothing to do. */
+int captra_image_members(int b, int h, int w, int cap, int border, int negate_z, const int *depth, const unsigned char *mask,
+                         const unsigned char *coord, const double *kinv, float *src, float *tgt, int *labels, int *pix, int *counts,
+                         captra_stream_t stream);
 
 /* Ragged batch of the same operation: the clouds are padded to n_stride points each (xyz (B,n_stride,3)) and cloud i
  * samples m of its FIRST n_per_cloud[i] points (device array of B ints, 1 <= n_per_cloud[i] <= n_stride; NULL = all
@@ -987,6 +1016,7 @@ void captra_sa1_stream_set_fine(int centres); /* level-1 stream kernel: trailing
 void captra_sa1_stream_set_whole(int windows); /* level-1 stream kernel: bits 0-7 = leading windows of 32 centres handed out as one ticket for all three scales (default 0), bit 8 = three scale tickets per window instead of two */
 void captra_sa_bf16_set_variant(int v);     /* bf16 SA scales: bit 0 = small-input scales without gather prefetch / fragment ring, bit 3 = SA2 scales on
                                                sa_bf16_kernel; bits 4.. (ablations with WRONG results, timing only) exist in -DCAPTRA_ABLATIONS=1 builds only */
+void captra_image_members_set_split(int n); /* captra_image_members: workgroups per image (0 = default: as many as fill the device twice, shares of >= 4096 pixels) */
 void captra_neck_chain_set_split(int n); /* captra_neck_chain_bf16, three-layer modules: workgroups sharing the last layer of a position tile (1 / 2 / 4, default 4) */
 void captra_query_and_group_set_shape(int mcb, int cc); /* captra_query_and_group: centres per workgroup, channels per chunk (0 = heuristic) */
 void captra_group_set_shape(int lds_kb, int ccmax, int ppb); /* group_points: staging budget (KiB, <= 64), channels per workgroup, positions per
