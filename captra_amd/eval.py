@@ -154,6 +154,18 @@ def image_fit_table(name: str, data: dict) -> list:
     return [f"{name}: members {r['members']}; used {r['used']}; holes {r['holes']}; inliers {r['inliers']}; valid {'yes' if r['valid'] else 'no'}"]
 
 
+# the options' records a result pickle may carry, in the order they are printed: (pickle key, its table, the heading -- {tests}: the
+# inlier tests the runs' guards used)
+RECORD_TABLES = (
+    ("guard", guard_table, "track guard ({tests} inlier test), frames per trajectory and part:"),
+    ("st_fit", st_fit_table, "robust scale / translation fit (track_cfg/st_fit), frames per trajectory and part:"),
+    ("rot_pool", rot_pool_table, "consensus rotation read-out (track_cfg/rot_pool), per trajectory and part:"),
+    ("otf_thin", otf_thin_table, "re-crop lists thinned on the device (track_cfg/otf_thin), frames per trajectory:"),
+    ("depth_filter", depth_filter_table, "flying depth pixels removed at upload (track_cfg/depth_filter), per trajectory:"),
+    ("image_fit", image_fit_table, "first pose fitted from frame 0's images (init_frame/image_fit), per trajectory:"),
+)
+
+
 def write_csv(errors: dict, path: str) -> None:
     keys = list(next(iter(errors.values())).keys())
     with open(path, "w") as f:
@@ -179,24 +191,16 @@ def main(argv=None) -> dict:
     del args.eval_device
     cfg = get_config(args, save=False)
     data_path = pjoin(cfg["experiment_dir"], "results", "data")
-    errors, guard_lines, guard_tests, st_lines, rot_lines, thin_lines, depth_lines, image_lines = {}, [], set(), [], [], [], [], []
+    errors, lines, guard_tests = {}, {key: [] for key, _, _ in RECORD_TABLES}, set()
     for raw in sorted(os.listdir(data_path)):
         with open(pjoin(data_path, raw), "rb") as f:
             data = pickle.load(f)
         errors.update(eval_data(raw.rsplit(".", 1)[0], data, cfg["obj_info"], device))
+        for key, table, _ in RECORD_TABLES:
+            if key in data:
+                lines[key] += table(raw.rsplit(".", 1)[0], data)
         if "guard" in data:
-            guard_lines += guard_table(raw.rsplit(".", 1)[0], data)
             guard_tests.add(guard_test_name(data))
-        if "st_fit" in data:
-            st_lines += st_fit_table(raw.rsplit(".", 1)[0], data)
-        if "rot_pool" in data:
-            rot_lines += rot_pool_table(raw.rsplit(".", 1)[0], data)
-        if "otf_thin" in data:
-            thin_lines += otf_thin_table(raw.rsplit(".", 1)[0], data)
-        if "depth_filter" in data:
-            depth_lines += depth_filter_table(raw.rsplit(".", 1)[0], data)
-        if "image_fit" in data:
-            image_lines += image_fit_table(raw.rsplit(".", 1)[0], data)
     if not errors:
         raise SystemExit(f"no result pickles under {data_path}")
     err_path = pjoin(cfg["experiment_dir"], "results", "err.pkl")
@@ -206,30 +210,11 @@ def main(argv=None) -> dict:
     avg = {k: float(np.mean([row[k] for row in errors.values()])) for k in next(iter(errors.values()))}
     for k, v in avg.items():
         print(f"{k}: {v}")
-    if guard_lines:
-        print(f"track guard ({' / '.join(sorted(guard_tests))} inlier test), frames per trajectory and part:")
-        for line in guard_lines:
-            print("  " + line)
-    if st_lines:
-        print("robust scale / translation fit (track_cfg/st_fit), frames per trajectory and part:")
-        for line in st_lines:
-            print("  " + line)
-    if rot_lines:
-        print("consensus rotation read-out (track_cfg/rot_pool), per trajectory and part:")
-        for line in rot_lines:
-            print("  " + line)
-    if thin_lines:
-        print("re-crop lists thinned on the device (track_cfg/otf_thin), frames per trajectory:")
-        for line in thin_lines:
-            print("  " + line)
-    if depth_lines:
-        print("flying depth pixels removed at upload (track_cfg/depth_filter), per trajectory:")
-        for line in depth_lines:
-            print("  " + line)
-    if image_lines:
-        print("first pose fitted from frame 0's images (init_frame/image_fit), per trajectory:")
-        for line in image_lines:
-            print("  " + line)
+    for key, _, heading in RECORD_TABLES:
+        if lines[key]:
+            print(heading.format(tests=" / ".join(sorted(guard_tests))))
+            for line in lines[key]:
+                print("  " + line)
     return avg
 
 

@@ -30,6 +30,7 @@ import torch.nn as nn
 
 from . import fused
 from . import graph as G
+from . import track_options as O
 from .networks import CoordNet, PartCanonNet, _canonicalize
 from .nocs_otf import DET_KEYS
 from .pose_utils.part_dof_utils import add_noise_to_part_dof, consume_noise_draws, eval_part_full, part_model_batch_to_part
@@ -109,14 +110,6 @@ def _frame_names(frame):
     return [p.split(".")[-2].split("/")[-1] for p in frame["meta"]["path"]]
 
 
-# init_frame/fit: the inlier distance of the first-pose fit as a fraction of data_radius -- 3 mm at the NOCS crops' 0.6 m: the
-# reference's preprocessing uses 1 mm on rendered (exact) maps (align_pose.py:49), sensor depth at 1 m is noisy at the millimetre
-INIT_FIT_INLIER_TH = 0.005
-GUARD_KEYS = ("count", "inliers", "rms", "verdict")     # a frame's guard record: (B,P) tensors (pose_utils/pose_fit.py)
-ROT_POOL_KEYS = ("inliers", "count")                    # a frame's record of the consensus rotation read-out: (B,P) int32 tensors
-ST_FIT_KEYS = ("inliers", "valid")                      # a frame's record of the robust scale / translation fit: (B,P) int32 tensors
-
-
 class EvalTrackModel(BaseModel):
     def __init__(self, cfg):
         super().__init__(cfg)
@@ -125,53 +118,20 @@ class EvalTrackModel(BaseModel):
         self.tree = cfg["obj_tree"]
         self.root = [p for p in range(len(self.tree)) if self.tree[p] == -1][0]
         self.gt_init = cfg["init_frame"]["gt"]
-        # init_frame: {fit: True}: the first pose is FITTED to frame 0's own NOCS map, labels and points (RANSAC similarity fit,
-        # csrc/pose_ransac.hip) -- no pose annotation is needed to start a track.  inlier_th is a fraction of data_radius (default
-        # INIT_FIT_INLIER_TH); num_hyps hypotheses drawn in the kernel from `seed`.  Absent / False: nothing changes.
-        self.fit_init = bool(cfg["init_frame"].get("fit", False))
-        self.fit_init_cfg = {"inlier_th": float(cfg["init_frame"].get("inlier_th", INIT_FIT_INLIER_TH)) * float(cfg["data_radius"]),
-                             "num_hyps": int(cfg["init_frame"].get("num_hyps", 64)), "seed": int(cfg["init_frame"].get("seed", 0))}
-        # init_frame: {yaxis_only: True} / track_cfg: {guard: {yaxis_only: True}}: the AXIS-ONLY inlier test (include/captra_hip.h,
-        # captra_part_fit_guard_sym) for a symmetric category, whose tracked in-plane angle carries no information.  Absent / False:
-        # today's launches and records; True on a category that is not symmetric is an error.
-        self.fit_init_yaxis = self._yaxis_only(cfg, cfg["init_frame"], "init_frame/yaxis_only")
-        # init_frame: {image_fit: True, border: 0, cap: 16384, coord_negate_z: False}: the first pose is fitted to frame 0's IMAGES -- the
-        # depth image, the instance mask and the NOCS coordinate image of meta['pre_fetched'], the three outputs of a NOCS-style
-        # detector (csrc/image_fit.hip turns them into correspondences, the same RANSAC fit as init_frame/fit reads them with its
-        # inlier_th, num_hyps, seed and yaxis_only) -- so a track starts from images alone.  The fit is recorded (pred_dict / pickle
-        # 'image_fit').  Absent / False: no launch, no tensor, no pickle entry.
-        self.image_fit = self._image_fit_cfg(cfg)
+        # the opt-in features, each parsed once (track_options.py says what each one is); None = off: no launch, no tensor, no pickle entry
+        self.fit_init = bool(cfg["init_frame"].get("fit", False))          # the first pose fitted to frame 0's NOCS map
+        self.fit_init_cfg = O.init_fit_cfg(cfg)
+        self.fit_init_yaxis = O.yaxis_only(cfg, cfg["init_frame"], "init_frame/yaxis_only")
+        self.image_fit = O.image_fit_cfg(cfg)                              # the first pose fitted to frame 0's images
         self._fit_fallback_logged = False
-        # track_cfg: {guard: {...}}: every step checks the pose it produced against the frame's own NOCS map, labels and points
-        # (csrc/pose_guard.hip, one launch behind the pose fit, captured with the step) and, with refit, re-fits a part found lost
-        # by the first-pose estimator.  Absent: no launch, no tensor, no pickle entry.
-        self.guard = self._guard_cfg(cfg)
+        self.guard = O.guard_cfg(cfg)                                      # every step's pose checked, a lost part re-fitted
         self._warn_full_rotation_test(cfg)
-        # track_cfg: {st_fit: {ransac: True, ...}}: every step's scale / translation by RANSAC with RotationNet's rotation given
-        # (csrc/pose_st_ransac.hip, in place of the one-pass fit's launch, captured with the step); the inlier test is the axis-only
-        # one for a symmetric category.  The guard, when on, judges the pose this fit produced.  Absent / ransac: False: nothing
-        # is launched, no tensor, no pickle entry.
-        self.st_fit = self.net.st_fit = self._st_fit_cfg(cfg)
-        # track_cfg: {rot_pool: {consensus: True, angle_th: <degrees>, ...}}: every step's rotation from the consensus of RotationNet's
-        # per-point votes (csrc/rot_consensus.hip, in place of the plain read-out's launch, captured with the step); the scale /
-        # translation fit and the guard consume that rotation unchanged.  Absent / consensus: False: nothing is launched, no tensor,
-        # no pickle entry.
-        self.rot_pool = self.net.rot_pool = self._rot_pool_cfg(cfg)
+        self.st_fit = self.net.st_fit = O.st_fit_cfg(cfg)                  # every step's scale / translation by RANSAC
+        self.rot_pool = self.net.rot_pool = O.rot_pool_cfg(cfg)            # every step's rotation from the votes' consensus
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
-        # track_cfg: {otf_thin: {device: True, seed: <int>}}: the re-crop thins a candidate list of more than 5 N ball members ON THE
-        # DEVICE (csrc/otf_thin.hip: a counter-based draw keyed by seed, trajectory and frame, the kept members in pixel order -- not
-        # numpy's permutation, see include/captra_hip.h) instead of on the host, so a close-up crop is no rare-path instance of the
-        # sync-free loop; the frames' thinned instances are recorded (pred_dict / pickle 'otf_thin').  Absent / device: False: nothing
-        # is launched, no tensor, no pickle entry, numpy's generator is consumed as before.
-        self.otf_thin = self._otf_thin_cfg(cfg)
+        self.otf_thin = O.otf_thin_cfg(cfg)                                # the re-crop's over-long lists thinned on the device
         self._otf_thin_rec = {}             # frame -> {first trajectory of a slice: its thinned flags (b,) int32 on the device}
-        # track_cfg: {depth_filter: {window: 2, abs_mm: <int>, rel_permille: 0, min_support: <int>}}: every uploaded depth image loses
-        # its flying pixels -- those that fewer than min_support of their image neighbours support in depth (csrc/depth_filter.hip,
-        # include/captra_hip.h: captra_depth_support_filter) -- ONCE, when the frame is put on the device (set_data): one launch per
-        # frame over all trajectories, outside the step, the lanes and the replay of a flagged frame, which all read the filtered
-        # image.  The removed pixels are recorded per frame and trajectory (pred_dict / pickle 'depth_filter').  Absent: nothing is
-        # launched, no tensor, no pickle entry, the upload is used as it is.
-        self.depth_filter = self._depth_filter_cfg(cfg)
+        self.depth_filter = O.depth_filter_cfg(cfg)                        # flying pixels out of every uploaded depth image
         self.radius = cfg["data_radius"]
         self.det_category = cfg["obj_category"]          # nocs2d_label: the class id the frame's detections are matched against
         self._det_missing_logged = False
@@ -215,122 +175,6 @@ class EvalTrackModel(BaseModel):
         self.otf_lanes = bool(cfg.get("otf_lanes", True))
         self._graph = None
         self._graph_key = None
-
-    @staticmethod
-    def _guard_cfg(cfg):
-        g = cfg["track_cfg"].get("guard")
-        if g is None:
-            return None
-        if g.get("lost_below") is None:
-            raise ValueError("track_cfg/guard needs lost_below (the inlier fraction below which a part counts as lost): it has no default")
-        from .pose_utils.pose_fit import lost_ratio
-        # lost_below as the two ints the kernel compares with, converted once (raises on a value outside [0, 1])
-        out = {"refit": bool(g.get("refit", False)), "lost_below": lost_ratio(g["lost_below"]),
-               "inlier_th": float(g.get("inlier_th", INIT_FIT_INLIER_TH)) * float(cfg["data_radius"]),
-               "min_members": int(g.get("min_members", 4)), "num_hyps": int(g.get("num_hyps", cfg["init_frame"].get("num_hyps", 64))),
-               "seed": int(g.get("seed", cfg["init_frame"].get("seed", 0)))}
-        if EvalTrackModel._yaxis_only(cfg, g, "track_cfg/guard/yaxis_only"):
-            out["yaxis_only"] = True            # (carried only when on)
-        return out
-
-    @staticmethod
-    def _st_fit_cfg(cfg):
-        """track_cfg/st_fit, parsed once: None when absent or ransac is not set; inlier_th is a fraction of data_radius (the guard's
-        default), num_hyps and seed default to init_frame's, as the guard's do."""
-        s = cfg["track_cfg"].get("st_fit")
-        if s is None or not s.get("ransac", False):
-            return None
-        frac = s.get("inlier_th")
-        frac = INIT_FIT_INLIER_TH if frac is None else float(frac)
-        num_hyps = s.get("num_hyps")
-        num_hyps = int(cfg["init_frame"].get("num_hyps", 64) if num_hyps is None else num_hyps)
-        seed = s.get("seed")
-        seed = int(cfg["init_frame"].get("seed", 0) if seed is None else seed)
-        if not (frac > 0.0 and np.isfinite(frac)):
-            raise ValueError(f"track_cfg/st_fit/inlier_th must be a positive fraction of data_radius, got {s.get('inlier_th')!r}")
-        if not 1 <= num_hyps <= 256:
-            raise ValueError(f"track_cfg/st_fit/num_hyps must be in [1, 256] (the kernel's limit), got {num_hyps}")
-        if seed < 0:
-            raise ValueError(f"track_cfg/st_fit/seed must not be negative, got {seed}")
-        return {"inlier_th": frac * float(cfg["data_radius"]), "num_hyps": num_hyps, "seed": seed}
-
-    @staticmethod
-    def _image_fit_cfg(cfg):
-        """init_frame/image_fit, parsed once: None when absent or not set, else {'cap', 'border', 'negate_z'} inside the kernels' ranges."""
-        from .nocs_otf import IMAGE_FIT_CAP, check_image_fit_params
-        f = cfg["init_frame"]
-        if not f.get("image_fit", False):
-            return None
-        if f.get("fit", False):
-            raise ValueError("init_frame/image_fit and init_frame/fit both fit the first pose, one from frame 0's images and one from its "
-                             "pre-cropped cloud: set one of them")
-        if int(cfg["num_parts"]) != 1:
-            raise ValueError(f"init_frame/image_fit fits one rigid object (a coordinate image describes one), this object has num_parts = "
-                             f"{cfg['num_parts']}")
-        cap, border = f.get("cap"), f.get("border")
-        cap, border = check_image_fit_params(IMAGE_FIT_CAP if cap is None else cap, 0 if border is None else border, prefix="init_frame/")
-        return {"cap": cap, "border": border, "negate_z": bool(f.get("coord_negate_z", False))}
-
-    @staticmethod
-    def _otf_thin_cfg(cfg):
-        """track_cfg/otf_thin, parsed once: None when absent or device is not set, else {'seed'}."""
-        t = cfg["track_cfg"].get("otf_thin")
-        if t is None or not t.get("device", False):
-            return None
-        seed = int(t.get("seed", 0) or 0)
-        if seed < 0:
-            raise ValueError(f"track_cfg/otf_thin/seed must not be negative, got {seed}")
-        return {"seed": seed}
-
-    @staticmethod
-    def _depth_filter_cfg(cfg):
-        """track_cfg/depth_filter, parsed once: None when absent, else {'window', 'abs_mm', 'rel_permille', 'min_support'} inside the
-        kernel's ranges.  abs_mm and min_support have no default: the right values depend on the sensor and on the window."""
-        from .nocs_otf import check_depth_filter_params
-        f = cfg["track_cfg"].get("depth_filter")
-        if f is None:
-            return None
-        if not cfg.get("nocs_otf", False):
-            raise ValueError("track_cfg/depth_filter filters the depth images the on-the-fly re-crop reads: it needs nocs_otf: True "
-                             "(without it there is no depth image)")
-        for key in ("abs_mm", "min_support"):
-            if f.get(key) is None:
-                raise ValueError(f"track_cfg/depth_filter needs track_cfg/depth_filter/{key}: it has no default")
-        window, rel = f.get("window"), f.get("rel_permille")
-        vals = check_depth_filter_params(2 if window is None else window, f["abs_mm"], 0 if rel is None else rel, f["min_support"],
-                                         prefix="track_cfg/depth_filter/")
-        return dict(zip(("window", "abs_mm", "rel_permille", "min_support"), vals))
-
-    @staticmethod
-    def _rot_pool_cfg(cfg):
-        """track_cfg/rot_pool, parsed once: None when absent or consensus is not set; angle_th (degrees) has no default -- the right
-        value depends on the trained network's vote scatter --, num_hyps and seed default to init_frame's, as st_fit's do."""
-        s = cfg["track_cfg"].get("rot_pool")
-        if s is None or not s.get("consensus", False):
-            return None
-        angle = s.get("angle_th")
-        if angle is None:
-            raise ValueError("track_cfg/rot_pool/consensus needs track_cfg/rot_pool/angle_th (degrees, inside (0, 180)): it has no default")
-        angle = float(angle)
-        num_hyps = s.get("num_hyps")
-        num_hyps = int(cfg["init_frame"].get("num_hyps", 64) if num_hyps is None else num_hyps)
-        seed = s.get("seed")
-        seed = int(cfg["init_frame"].get("seed", 0) if seed is None else seed)
-        if not 0.0 < angle < 180.0:
-            raise ValueError(f"track_cfg/rot_pool/angle_th must be an angle in degrees inside (0, 180), got {s.get('angle_th')!r}")
-        if not 1 <= num_hyps <= 256:
-            raise ValueError(f"track_cfg/rot_pool/num_hyps must be in [1, 256] (the kernel's limit), got {num_hyps}")
-        if seed < 0:
-            raise ValueError(f"track_cfg/rot_pool/seed must not be negative, got {seed}")
-        return {"angle_th": angle, "num_hyps": num_hyps, "seed": seed}
-
-    @staticmethod
-    def _yaxis_only(cfg, section, name) -> bool:
-        on = bool(section.get("yaxis_only", False))
-        if on and not cfg["obj_sym"]:
-            raise ValueError(f"{name}: the axis-only inlier test is for symmetric categories (obj_sym), category "
-                             f"{cfg['obj_category']} is not one: its in-plane angle is part of the pose")
-        return on
 
     def _warn_full_rotation_test(self, cfg):
         """Once per model object: a symmetric category judged by the full-rotation test."""
@@ -428,10 +272,14 @@ class EvalTrackModel(BaseModel):
         rot, scale, trans, valid, _ = part_fit_ransac_cn(first["labels"].int().contiguous(), src, first["points"].float().contiguous(),
                                                          num_hyps=self.fit_init_cfg["num_hyps"], inlier_th=self.fit_init_cfg["inlier_th"],
                                                          seed=self.fit_init_cfg["seed"], target_mean=mean, yaxis_only=self.fit_init_yaxis)
+        return self._valid_fits("init_frame/fit", rot, scale, trans, valid, fallback)
+
+    def _valid_fits(self, option, rot, scale, trans, valid, fallback):
+        """The first poses of `option`'s fit, `fallback` where a fit is not valid (said once per model object)."""
         if not self._fit_fallback_logged and not bool(valid.all()):
             self._fit_fallback_logged = True
-            logging.getLogger(__name__).warning("init_frame/fit: %d of %d first-pose fits are invalid; those parts start from the "
-                                                "annotated pose", int((~valid).sum()), valid.numel())
+            logging.getLogger(__name__).warning("%s: %d of %d first-pose fits are invalid; those parts start from the "
+                                                "annotated pose", option, int((~valid).sum()), valid.numel())
         return {"rotation": torch.where(valid[..., None, None], rot, fallback["rotation"]),
                 "scale": torch.where(valid, scale, fallback["scale"]),
                 "translation": torch.where(valid[..., None, None], trans, fallback["translation"])}
@@ -457,13 +305,7 @@ class EvalTrackModel(BaseModel):
         counts = mem["counts"]
         self._image_fit_rec = {"members": counts[:, 0].contiguous(), "used": counts[:, 1].contiguous(), "holes": counts[:, 2].contiguous(),
                                "inliers": info["num_inliers"][:, 0].contiguous(), "valid": valid[:, 0].int()}
-        if not self._fit_fallback_logged and not bool(valid.all()):
-            self._fit_fallback_logged = True
-            logging.getLogger(__name__).warning("init_frame/image_fit: %d of %d first-pose fits are invalid; those parts start from the "
-                                                "annotated pose", int((~valid).sum()), valid.numel())
-        return {"rotation": torch.where(valid[..., None, None], rot, fallback["rotation"]),
-                "scale": torch.where(valid, scale, fallback["scale"]),
-                "translation": torch.where(valid[..., None, None], trans, fallback["translation"])}
+        return self._valid_fits("init_frame/image_fit", rot, scale, trans, valid, fallback)
 
     @contextlib.contextmanager
     def _step_context(self, points, allow_split_k=True):
@@ -587,13 +429,10 @@ class EvalTrackModel(BaseModel):
             input["shared_geometry"] = (self.npcs_net.last_canon, self.npcs_net.backbone.last_geom)
         out = self.net(input, test_mode=True)
         pose = out["part"]
-        if self.st_fit is not None:
-            # the robust fit's record joins CoordinateNet's maps (`st_*`), so it travels with them through every batch form
-            for k in ST_FIT_KEYS:
-                npcs_pred["st_" + k] = out["st_fit"][k]
-        if self.rot_pool is not None:
-            for k in ROT_POOL_KEYS:                 # (likewise `rot_*`)
-                npcs_pred["rot_" + k] = out["rot_pool"][k]
+        for name in ("st_fit", "rot_pool"):
+            if getattr(self, name) is not None:
+                # the option's record joins CoordinateNet's maps (`st_*`, `rot_*`), so it travels with them through every batch form
+                O.put_record(npcs_pred, name, out[name])
         return pose if self.guard is None else self._guard_step(input, npcs_pred, pose)
 
     def _guard_step(self, input, npcs_pred, pose):
@@ -608,8 +447,7 @@ class EvalTrackModel(BaseModel):
                                        input["points_mean"], pose, inlier_th=g["inlier_th"], lost_below=g["lost_below"],
                                        min_members=g["min_members"], refit=g["refit"], num_hyps=g["num_hyps"], seed=g["seed"],
                                        b0=int(input.get("b0", 0)), yaxis_only=g.get("yaxis_only", False))
-        for k in GUARD_KEYS:
-            npcs_pred["guard_" + k] = info[k]
+        O.put_record(npcs_pred, "guard", info)
         return pose
 
     # ---- the two networks side by side -------------------------------------------------------------------------------
@@ -908,9 +746,7 @@ class EvalTrackModel(BaseModel):
         batch-wide records on the caller's stream."""
         feed = self.feed_dict
         pred_poses, npcs_pred = [self._initial_pose()], [None]
-        guard = {}                          # frame -> its guard record (guard on)
-        st_fit = {}                         # frame -> the robust fit's record (track_cfg/st_fit on)
-        rot_pool = {}                       # frame -> the consensus read-out's record (track_cfg/rot_pool on)
+        records = {name: {} for name in O.STEP_RECORDS if getattr(self, name) is not None}     # option that is on -> {frame: its record}
         self._otf_thin_rec = {}
         if self.frame_hook is not None:
             self.frame_hook(0, pred_poses[0])
@@ -924,12 +760,7 @@ class EvalTrackModel(BaseModel):
                 frames = self._batch_frames
             with torch.no_grad():
                 run_frame, commit, poses, bounds, join = frames(pred_poses[0])
-                if self.guard is not None:
-                    commit = self._commit_with_record(commit, guard, "guard_", GUARD_KEYS)
-                if self.st_fit is not None:
-                    commit = self._commit_with_record(commit, st_fit, "st_", ST_FIT_KEYS)
-                if self.rot_pool is not None:
-                    commit = self._commit_with_record(commit, rot_pool, "rot_", ROT_POOL_KEYS)
+                commit = O.commit_with_records(commit, records)
                 pending = None                  # (frame, poses that entered it, its deferred checks)
 
                 def settle():
@@ -970,36 +801,20 @@ class EvalTrackModel(BaseModel):
                 if join is not None:
                     join()
         self.pred_dict = {"poses": pred_poses, "npcs_pred": npcs_pred}
-        if self.guard is not None:
-            self.pred_dict["guard"] = [None] + [guard[i] for i in range(1, len(feed))]
-        if self.st_fit is not None:
-            self.pred_dict["st_fit"] = [None] + [st_fit[i] for i in range(1, len(feed))]
-        if self.rot_pool is not None:
-            self.pred_dict["rot_pool"] = [None] + [rot_pool[i] for i in range(1, len(feed))]
+        # the options' records (track_options.py), each only when its option is on: a step's, the host loop's two, frame 0's one
+        for name, record in records.items():
+            self.pred_dict[name] = [None] + [record[i] for i in range(1, len(feed))]
         if self.otf_thin is not None and self.nocs_otf:
-            # per frame: which trajectories' lists were thinned, (B,) int32 -- its sum is the frame's count of thinned instances
-            rec = self._otf_thin_rec
+            rec = self._otf_thin_rec        # (a lane wrote its slice of the frame: the slices in batch order)
             self.pred_dict["otf_thin"] = [None] + [next(iter(rec[i].values())) if len(rec[i]) == 1 else torch.cat([rec[i][k] for k in sorted(rec[i])])
                                                    for i in range(1, len(feed))]
         if self.depth_filter is not None:
-            # per frame: the pixels the filter set to 0 in every trajectory's image, (B,) int32 (None: a frame without depth)
-            self.pred_dict["depth_filter"] = [f.get("depth_filter_removed") for f in feed]
+            self.pred_dict["depth_filter"] = [f.get("depth_filter_removed") for f in feed]       # (None: a frame without depth)
         if self.image_fit is not None:
-            # frame 0's fit: members, used, holes, inliers, valid, (B,) int32 each
             self.pred_dict["image_fit"] = self._image_fit_rec
         self.check_l1_stream()
         if save:
             self._save(list(map(_frame_names, feed)))
-
-    @staticmethod
-    def _commit_with_record(commit, records, prefix, keys):
-        """`commit` of a batch form, with the frame's record (the guard's `guard_*`, the robust fit's `st_*`, the consensus read-out's `rot_*`) taken out of
-        CoordinateNet's maps into records[frame]."""
-        def wrapped(i, result):
-            npcs, pose = commit(i, result)
-            records[i] = {k: npcs.pop(prefix + k) for k in keys}
-            return npcs, pose
-        return wrapped
 
     def _save(self, frame_nums):
         """Per-trajectory pickle {'pred': {'poses','corners'}, 'gt': {'poses','corners'}, 'frame_nums'}
@@ -1026,22 +841,7 @@ class EvalTrackModel(BaseModel):
         save_dict = {"pred": {"poses": [to_np(p) for p in self.pred_dict["poses"]], "corners": corner_list},
                      "gt": {"poses": [to_np(f["gt_part"]) for f in self.feed_dict], "corners": gt_corners},
                      "frame_nums": frame_nums}
-        if self.guard is not None:
-            save_dict["guard"] = [None if g is None else {k: v.detach().cpu().numpy() for k, v in g.items()} for g in self.pred_dict["guard"]]
-            if self.guard.get("yaxis_only", False):
-                # which test counted the inliers: one boolean, in the slot of frame 0 (which has no record: None otherwise), only
-                # when on -- the frames' records keep their four keys
-                save_dict["guard"][0] = {"yaxis_only": np.ones(len(self.feed_dict[0]["meta"]["path"]), bool)}
-        if self.st_fit is not None:
-            save_dict["st_fit"] = [None if r is None else {k: v.detach().cpu().numpy() for k, v in r.items()} for r in self.pred_dict["st_fit"]]
-        if self.rot_pool is not None:
-            save_dict["rot_pool"] = [None if r is None else {k: v.detach().cpu().numpy() for k, v in r.items()} for r in self.pred_dict["rot_pool"]]
-        if "otf_thin" in self.pred_dict:
-            save_dict["otf_thin"] = [None if r is None else {"thinned": r.detach().cpu().numpy()} for r in self.pred_dict["otf_thin"]]
-        if "depth_filter" in self.pred_dict:
-            save_dict["depth_filter"] = [None if r is None else {"removed": r.detach().cpu().numpy()} for r in self.pred_dict["depth_filter"]]
-        if "image_fit" in self.pred_dict:
-            save_dict["image_fit"] = {k: v.detach().cpu().numpy() for k, v in self.pred_dict["image_fit"].items()}
+        save_dict.update(O.records_to_numpy(self.pred_dict, guard_yaxis_only=self.guard is not None and self.guard.get("yaxis_only", False)))
         records = []
         for i, path in enumerate(self.feed_dict[0]["meta"]["path"]):
             instance, track_num = path.split(".")[-2].split("/")[-3:-1]

@@ -23,26 +23,26 @@ _FLAGS = [  # (name, type, default)
     ("network/pwm_num", int, None),
     ("init_frame/gt", boolean_string, None), ("init_frame/fit", boolean_string, None), ("nocs_otf", boolean_string, None),
     ("track_cfg/gt_label", boolean_string, None), ("track_cfg/nocs2d_label", boolean_string, None), ("track_cfg/nocs2d_path", str, None),
-    # track health (model.py: EvalTrackModel.guard); lost_below has no default
+    # track health (track_options.py: guard_cfg); lost_below has no default
     ("track_cfg/guard/refit", boolean_string, None), ("track_cfg/guard/lost_below", float, None), ("track_cfg/guard/inlier_th", float, None),
     ("track_cfg/guard/min_members", int, None), ("track_cfg/guard/num_hyps", int, None), ("track_cfg/guard/seed", int, None),
     # the axis-only inlier test of the symmetric categories, in the guard and in the first-pose fit (init_frame/fit).  Not given = not
     # in the namespace at all (argparse.SUPPRESS): the key reaches the configuration only when it was written
     ("track_cfg/guard/yaxis_only", boolean_string, argparse.SUPPRESS), ("init_frame/yaxis_only", boolean_string, argparse.SUPPRESS),
-    # the first pose fitted from frame 0's depth, mask and NOCS coordinate image (model.py: EvalTrackModel.image_fit); off unless image_fit
+    # the first pose fitted from frame 0's depth, mask and NOCS coordinate image (track_options.py: image_fit_cfg); off unless image_fit
     # is True.  Not given = not in the namespace at all, like yaxis_only
     ("init_frame/image_fit", boolean_string, argparse.SUPPRESS), ("init_frame/border", int, argparse.SUPPRESS),
     ("init_frame/cap", int, argparse.SUPPRESS), ("init_frame/coord_negate_z", boolean_string, argparse.SUPPRESS),
-    # the robust scale / translation fit of every step (model.py: EvalTrackModel.st_fit); off unless ransac is True
+    # the robust scale / translation fit of every step (track_options.py: st_fit_cfg); off unless ransac is True
     ("track_cfg/st_fit/ransac", boolean_string, None), ("track_cfg/st_fit/inlier_th", float, None), ("track_cfg/st_fit/num_hyps", int, None),
     ("track_cfg/st_fit/seed", int, None),
-    # the consensus rotation read-out of every step (model.py: EvalTrackModel.rot_pool); off unless consensus is True, and then angle_th
+    # the consensus rotation read-out of every step (track_options.py: rot_pool_cfg); off unless consensus is True, and then angle_th
     # (degrees) is required
     ("track_cfg/rot_pool/consensus", boolean_string, None), ("track_cfg/rot_pool/angle_th", float, None),
     ("track_cfg/rot_pool/num_hyps", int, None), ("track_cfg/rot_pool/seed", int, None),
-    # the re-crop's over-long candidate lists thinned on the device (model.py: EvalTrackModel.otf_thin); off unless device is True
+    # the re-crop's over-long candidate lists thinned on the device (track_options.py: otf_thin_cfg); off unless device is True
     ("track_cfg/otf_thin/device", boolean_string, None), ("track_cfg/otf_thin/seed", int, None),
-    # flying depth pixels removed from every uploaded depth image (model.py: EvalTrackModel.depth_filter); on when any of the four is
+    # flying depth pixels removed from every uploaded depth image (track_options.py: depth_filter_cfg); on when any of the four is
     # given, and then abs_mm (millimetres) and min_support are required
     ("track_cfg/depth_filter/window", int, None), ("track_cfg/depth_filter/abs_mm", int, None),
     ("track_cfg/depth_filter/rel_permille", int, None), ("track_cfg/depth_filter/min_support", int, None),

@@ -1,0 +1,199 @@
+"""The track loop's opt-in features, as far as they are plumbing: each option's section of the configuration parsed once into the
+dict `EvalTrackModel` keeps (None = off: no launch, no tensor, no pickle entry), and ONE description of the records the options
+leave per frame: how they travel inside CoordinateNet's maps, are listed in `pred_dict` and laid out in the result pickle."""
+import numpy as np
+
+# init_frame/fit: the inlier distance of the first-pose fit as a fraction of data_radius -- 3 mm at the NOCS crops' 0.6 m: the
+# reference's preprocessing uses 1 mm on rendered (exact) maps (align_pose.py:49), sensor depth at 1 m is noisy at the millimetre
+INIT_FIT_INLIER_TH = 0.005
+
+
+# ---- the parsers: cfg -> None (off) or the option's dict --------------------------------------------------------------------
+def _draws(cfg, section, check=None):
+    """(num_hyps, seed) of a RANSAC option: the section's own, else init_frame's, else (64, 0); check = the section's name: in range too."""
+    num_hyps, seed = section.get("num_hyps"), section.get("seed")
+    num_hyps = int(cfg["init_frame"].get("num_hyps", 64) if num_hyps is None else num_hyps)
+    seed = int(cfg["init_frame"].get("seed", 0) if seed is None else seed)
+    if check is not None and not 1 <= num_hyps <= 256:
+        raise ValueError(f"{check}/num_hyps must be in [1, 256] (the kernel's limit), got {num_hyps}")
+    if check is not None and seed < 0:
+        raise ValueError(f"{check}/seed must not be negative, got {seed}")
+    return num_hyps, seed
+
+
+def yaxis_only(cfg, section, name) -> bool:
+    """init_frame: {yaxis_only: True} / track_cfg: {guard: {yaxis_only: True}}: the AXIS-ONLY inlier test (include/captra_hip.h,
+    captra_part_fit_guard_sym) for a symmetric category, whose tracked in-plane angle carries no information.  Absent / False:
+    today's launches and records; True on a category that is not symmetric is an error."""
+    on = bool(section.get("yaxis_only", False))
+    if on and not cfg["obj_sym"]:
+        raise ValueError(f"{name}: the axis-only inlier test is for symmetric categories (obj_sym), category "
+                         f"{cfg['obj_category']} is not one: its in-plane angle is part of the pose")
+    return on
+
+
+def init_fit_cfg(cfg):
+    """init_frame: {fit: True}: the first pose is FITTED to frame 0's own NOCS map, labels and points (RANSAC similarity fit,
+    csrc/pose_ransac.hip) -- no pose annotation is needed to start a track.  inlier_th is a fraction of data_radius (default
+    INIT_FIT_INLIER_TH); num_hyps hypotheses drawn in the kernel from `seed`.  (Parsed always: init_frame/image_fit reads them too.)"""
+    num_hyps, seed = _draws(cfg, {})
+    return {"inlier_th": float(cfg["init_frame"].get("inlier_th", INIT_FIT_INLIER_TH)) * float(cfg["data_radius"]), "num_hyps": num_hyps, "seed": seed}
+
+
+def image_fit_cfg(cfg):
+    """init_frame: {image_fit: True, border: 0, cap: 16384, coord_negate_z: False}: the first pose is fitted to frame 0's IMAGES -- the
+    depth image, the instance mask and the NOCS coordinate image of meta['pre_fetched'], the three outputs of a NOCS-style
+    detector (csrc/image_fit.hip turns them into correspondences, the same RANSAC fit as init_frame/fit reads them with its
+    inlier_th, num_hyps, seed and yaxis_only) -- so a track starts from images alone.  The fit is recorded (pred_dict / pickle
+    'image_fit').  None when absent or not set, else {'cap', 'border', 'negate_z'} inside the kernels' ranges."""
+    from .nocs_otf import IMAGE_FIT_CAP, check_image_fit_params
+    f = cfg["init_frame"]
+    if not f.get("image_fit", False):
+        return None
+    if f.get("fit", False):
+        raise ValueError("init_frame/image_fit and init_frame/fit both fit the first pose, one from frame 0's images and one from its "
+                         "pre-cropped cloud: set one of them")
+    if int(cfg["num_parts"]) != 1:
+        raise ValueError(f"init_frame/image_fit fits one rigid object (a coordinate image describes one), this object has num_parts = "
+                         f"{cfg['num_parts']}")
+    cap, border = f.get("cap"), f.get("border")
+    cap, border = check_image_fit_params(IMAGE_FIT_CAP if cap is None else cap, 0 if border is None else border, prefix="init_frame/")
+    return {"cap": cap, "border": border, "negate_z": bool(f.get("coord_negate_z", False))}
+
+
+def guard_cfg(cfg):
+    """track_cfg: {guard: {...}}: every step checks the pose it produced against the frame's own NOCS map, labels and points
+    (csrc/pose_guard.hip, one launch behind the pose fit, captured with the step) and, with refit, re-fits a part found lost
+    by the first-pose estimator.  None when absent; lost_below has no default; inlier_th is a fraction of data_radius; num_hyps
+    and seed default to init_frame's and are NOT held to the kernel's ranges here."""
+    g = cfg["track_cfg"].get("guard")
+    if g is None:
+        return None
+    if g.get("lost_below") is None:
+        raise ValueError("track_cfg/guard needs lost_below (the inlier fraction below which a part counts as lost): it has no default")
+    from .pose_utils.pose_fit import lost_ratio
+    num_hyps, seed = _draws(cfg, {})
+    # lost_below as the two ints the kernel compares with, converted once (raises on a value outside [0, 1]); the draws by
+    # g.get(key, default), not through _draws: an explicit null is a TypeError here, as it always was
+    out = {"refit": bool(g.get("refit", False)), "lost_below": lost_ratio(g["lost_below"]),
+           "inlier_th": float(g.get("inlier_th", INIT_FIT_INLIER_TH)) * float(cfg["data_radius"]),
+           "min_members": int(g.get("min_members", 4)), "num_hyps": int(g.get("num_hyps", num_hyps)), "seed": int(g.get("seed", seed))}
+    if yaxis_only(cfg, g, "track_cfg/guard/yaxis_only"):
+        out["yaxis_only"] = True            # (carried only when on)
+    return out
+
+
+def st_fit_cfg(cfg):
+    """track_cfg: {st_fit: {ransac: True, ...}}: every step's scale / translation by RANSAC with RotationNet's rotation given
+    (csrc/pose_st_ransac.hip, in place of the one-pass fit's launch, captured with the step); the inlier test is the axis-only
+    one for a symmetric category.  The guard, when on, judges the pose this fit produced.  None when absent or ransac is not set;
+    inlier_th is a fraction of data_radius (the guard's default), num_hyps and seed default to init_frame's."""
+    s = cfg["track_cfg"].get("st_fit")
+    if s is None or not s.get("ransac", False):
+        return None
+    frac = s.get("inlier_th")
+    frac = INIT_FIT_INLIER_TH if frac is None else float(frac)
+    if not (frac > 0.0 and np.isfinite(frac)):
+        raise ValueError(f"track_cfg/st_fit/inlier_th must be a positive fraction of data_radius, got {s.get('inlier_th')!r}")
+    num_hyps, seed = _draws(cfg, s, check="track_cfg/st_fit")
+    return {"inlier_th": frac * float(cfg["data_radius"]), "num_hyps": num_hyps, "seed": seed}
+
+
+def rot_pool_cfg(cfg):
+    """track_cfg: {rot_pool: {consensus: True, angle_th: <degrees>, ...}}: every step's rotation from the consensus of RotationNet's
+    per-point votes (csrc/rot_consensus.hip, in place of the plain read-out's launch, captured with the step); the scale /
+    translation fit and the guard consume that rotation unchanged.  None when absent or consensus is not set; angle_th has no
+    default -- the right value depends on the trained network's vote scatter --, num_hyps and seed default to init_frame's."""
+    s = cfg["track_cfg"].get("rot_pool")
+    if s is None or not s.get("consensus", False):
+        return None
+    angle = s.get("angle_th")
+    if angle is None:
+        raise ValueError("track_cfg/rot_pool/consensus needs track_cfg/rot_pool/angle_th (degrees, inside (0, 180)): it has no default")
+    angle = float(angle)
+    if not 0.0 < angle < 180.0:
+        raise ValueError(f"track_cfg/rot_pool/angle_th must be an angle in degrees inside (0, 180), got {s.get('angle_th')!r}")
+    num_hyps, seed = _draws(cfg, s, check="track_cfg/rot_pool")
+    return {"angle_th": angle, "num_hyps": num_hyps, "seed": seed}
+
+
+def otf_thin_cfg(cfg):
+    """track_cfg: {otf_thin: {device: True, seed: <int>}}: the re-crop thins a candidate list of more than 5 N ball members ON THE
+    DEVICE (csrc/otf_thin.hip: a counter-based draw keyed by seed, trajectory and frame, the kept members in pixel order -- not
+    numpy's permutation, see include/captra_hip.h) instead of on the host, so a close-up crop is no rare-path instance of the
+    sync-free loop; the frames' thinned instances are recorded (pred_dict / pickle 'otf_thin').  None when absent or device is not
+    set (numpy's generator is consumed as before), else {'seed'}."""
+    t = cfg["track_cfg"].get("otf_thin")
+    if t is None or not t.get("device", False):
+        return None
+    seed = int(t.get("seed", 0) or 0)       # its own default, not init_frame's: the seed keys the thinning draw, not a RANSAC
+    if seed < 0:
+        raise ValueError(f"track_cfg/otf_thin/seed must not be negative, got {seed}")
+    return {"seed": seed}
+
+
+def depth_filter_cfg(cfg):
+    """track_cfg: {depth_filter: {window: 2, abs_mm: <int>, rel_permille: 0, min_support: <int>}}: every uploaded depth image loses
+    its flying pixels -- those that fewer than min_support of their image neighbours support in depth (csrc/depth_filter.hip,
+    include/captra_hip.h: captra_depth_support_filter) -- ONCE, when the frame is put on the device (set_data): one launch per
+    frame over all trajectories, outside the step, the lanes and the replay of a flagged frame, which all read the filtered
+    image.  The removed pixels are recorded per frame and trajectory (pred_dict / pickle 'depth_filter').  None when absent (the
+    upload is used as it is), else the four inside the kernel's ranges; abs_mm and min_support have no default: the right values
+    depend on the sensor and on the window."""
+    from .nocs_otf import check_depth_filter_params
+    f = cfg["track_cfg"].get("depth_filter")
+    if f is None:
+        return None
+    if not cfg.get("nocs_otf", False):
+        raise ValueError("track_cfg/depth_filter filters the depth images the on-the-fly re-crop reads: it needs nocs_otf: True "
+                         "(without it there is no depth image)")
+    for key in ("abs_mm", "min_support"):
+        if f.get(key) is None:
+            raise ValueError(f"track_cfg/depth_filter needs track_cfg/depth_filter/{key}: it has no default")
+    window, rel = f.get("window"), f.get("rel_permille")
+    vals = check_depth_filter_params(2 if window is None else window, f["abs_mm"], 0 if rel is None else rel, f["min_support"],
+                                     prefix="track_cfg/depth_filter/")
+    return dict(zip(("window", "abs_mm", "rel_permille", "min_support"), vals))
+
+
+# ---- the records: name in pred_dict and the pickle (and of the model attribute that switches the option on) -> ... ---------------
+# A step's records, (B,P) tensors per frame -> (the prefix its keys travel under inside CoordinateNet's maps, the keys)
+STEP_RECORDS = {"guard": ("guard_", ("count", "inliers", "rms", "verdict")),     # pose_utils/pose_fit.py
+                "st_fit": ("st_", ("inliers", "valid")),                         # int32
+                "rot_pool": ("rot_", ("inliers", "count"))}                      # int32
+# The host loop's records, ONE (B,) int32 tensor per frame (None: a frame without) -> the key that wraps it in the pickle.
+# otf_thin: which trajectories' lists were thinned (its sum: the frame's thinned instances); depth_filter: the pixels set to 0
+LOOP_RECORDS = {"otf_thin": "thinned", "depth_filter": "removed"}
+# (and frame 0's one-off "image_fit": a flat dict of (B,) int32 tensors -- members, used, holes, inliers, valid)
+
+
+def put_record(npcs_pred, name, values):
+    """A step record's values into CoordinateNet's maps, under the record's prefix."""
+    prefix, keys = STEP_RECORDS[name]
+    npcs_pred.update((prefix + k, values[k]) for k in keys)
+
+
+def commit_with_records(commit, records):
+    """`commit` of a batch form, with the frame's step records taken out of CoordinateNet's maps: records = {name: {}} of the
+    options that are on, filled as records[name][frame] = {key: tensor}."""
+    def wrapped(i, result):
+        npcs, pose = commit(i, result)
+        for name, frames in records.items():
+            prefix, keys = STEP_RECORDS[name]
+            frames[i] = {k: npcs.pop(prefix + k) for k in keys}
+        return npcs, pose
+    return wrapped if records else commit
+
+
+def records_to_numpy(pred_dict, guard_yaxis_only=False):
+    """The result pickle's entries for the records `pred_dict` carries (none: {}), as numpy: a step record as [None, {key: (B,P)}, ...],
+    a loop record as [None or {'thinned' / 'removed': (B,)}, ...], image_fit as a flat dict.  guard_yaxis_only: which test counted the
+    guard's inliers -- one boolean per trajectory in the slot of frame 0 (None otherwise), so the frames' records keep their four keys."""
+    to_np = lambda t: t.detach().cpu().numpy()
+    out = {name: [None if r is None else {k: to_np(v) for k, v in r.items()} for r in pred_dict[name]] for name in STEP_RECORDS if name in pred_dict}
+    if guard_yaxis_only and "guard" in out:
+        out["guard"][0] = {"yaxis_only": np.ones(len(pred_dict["poses"][0]["scale"]), bool)}
+    out.update({name: [None if r is None else {key: to_np(r)} for r in pred_dict[name]] for name, key in LOOP_RECORDS.items() if name in pred_dict})
+    if "image_fit" in pred_dict:
+        out["image_fit"] = {k: to_np(v) for k, v in pred_dict["image_fit"].items()}
+    return out

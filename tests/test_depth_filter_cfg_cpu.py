@@ -1,5 +1,5 @@
 """The configuration surface of track_cfg/depth_filter (flying depth pixels removed from every uploaded depth image): the flags,
-EvalTrackModel._depth_filter_cfg and every error it raises, the table of captra_amd.eval, the binding row, and synthetic's `flying`
+track_options.depth_filter_cfg and every error it raises, the table of captra_amd.eval, the binding row, and synthetic's `flying`
 (default = the shipped frames)."""
 import argparse
 
@@ -31,20 +31,20 @@ def test_parse_args_builds_the_depth_filter_cfg():
 
 def test_absent_option_is_none():
     from captra_amd.configs import make_config
-    from captra_amd.model import EvalTrackModel
-    assert EvalTrackModel._depth_filter_cfg(make_config("1")) is None
-    assert EvalTrackModel._depth_filter_cfg(make_config("1", nocs_otf=True)) is None
+    from captra_amd import track_options
+    assert track_options.depth_filter_cfg(make_config("1")) is None
+    assert track_options.depth_filter_cfg(make_config("1", nocs_otf=True)) is None
     cfg = make_config("1", nocs_otf=True)
     cfg["track_cfg"]["depth_filter"] = None
-    assert EvalTrackModel._depth_filter_cfg(cfg) is None
+    assert track_options.depth_filter_cfg(cfg) is None
 
 
 def test_defaults_and_parsed_values():
-    from captra_amd.model import EvalTrackModel
-    assert EvalTrackModel._depth_filter_cfg(_cfg(abs_mm=10, min_support=6)) == {"window": 2, "abs_mm": 10, "rel_permille": 0, "min_support": 6}
-    assert EvalTrackModel._depth_filter_cfg(_cfg(window=3, abs_mm=0, rel_permille=1000, min_support=48)) == {
+    from captra_amd import track_options
+    assert track_options.depth_filter_cfg(_cfg(abs_mm=10, min_support=6)) == {"window": 2, "abs_mm": 10, "rel_permille": 0, "min_support": 6}
+    assert track_options.depth_filter_cfg(_cfg(window=3, abs_mm=0, rel_permille=1000, min_support=48)) == {
         "window": 3, "abs_mm": 0, "rel_permille": 1000, "min_support": 48}
-    assert tuple(EvalTrackModel._depth_filter_cfg(_cfg(abs_mm=10, min_support=6))) == KEYS       # the wrapper's keyword order
+    assert tuple(track_options.depth_filter_cfg(_cfg(abs_mm=10, min_support=6))) == KEYS       # the wrapper's keyword order
 
 
 @pytest.mark.parametrize("section,word", [
@@ -63,15 +63,15 @@ def test_defaults_and_parsed_values():
     (dict(abs_mm=10.5, min_support=6), "abs_mm"),
 ])
 def test_values_outside_the_kernels_ranges_raise_at_construction(section, word):
-    from captra_amd.model import EvalTrackModel
+    from captra_amd import track_options
     with pytest.raises(ValueError, match="track_cfg/depth_filter.*" + word):
-        EvalTrackModel._depth_filter_cfg(_cfg(**section))
+        track_options.depth_filter_cfg(_cfg(**section))
 
 
 def test_the_option_needs_the_on_the_fly_re_crop():
-    from captra_amd.model import EvalTrackModel
+    from captra_amd import track_options
     with pytest.raises(ValueError, match="nocs_otf"):
-        EvalTrackModel._depth_filter_cfg(_cfg(nocs_otf=False, abs_mm=10, min_support=6))
+        track_options.depth_filter_cfg(_cfg(nocs_otf=False, abs_mm=10, min_support=6))
 
 
 def test_the_model_parses_the_option_when_it_is_built():

@@ -86,16 +86,17 @@ def test_parse_args_builds_the_guard_cfg():
 
 def test_model_needs_lost_below():
     from captra_amd.configs import make_config
-    from captra_amd.model import INIT_FIT_INLIER_TH, EvalTrackModel
+    from captra_amd import track_options
+    from captra_amd.track_options import INIT_FIT_INLIER_TH
     cfg = make_config("1")
-    assert EvalTrackModel._guard_cfg(cfg) is None
+    assert track_options.guard_cfg(cfg) is None
     with pytest.raises(ValueError, match="lost_below"):
-        EvalTrackModel._guard_cfg(make_config("1", **{"track_cfg/guard/refit": True}))
+        track_options.guard_cfg(make_config("1", **{"track_cfg/guard/refit": True}))
     with pytest.raises(ValueError, match="lost_below"):
         from captra_amd.trainer import Trainer
         Trainer(make_config("1", experiment_dir="/tmp/captra_test_exp", **{"track_cfg/guard/refit": True}))
     cfg = make_config("1", **{"track_cfg/guard/lost_below": 0.5})
-    g = EvalTrackModel._guard_cfg(cfg)
+    g = track_options.guard_cfg(cfg)
     assert g == {"refit": False, "lost_below": (1, 2), "inlier_th": INIT_FIT_INLIER_TH * cfg["data_radius"], "min_members": 4,
                  "num_hyps": 64, "seed": 0}
 

@@ -149,11 +149,11 @@ def test_parse_args_carries_both_keys_only_when_written():
 
 def test_guard_cfg_carries_the_key_only_when_on():
     from captra_amd.configs import make_config
-    from captra_amd.model import EvalTrackModel
-    g = EvalTrackModel._guard_cfg(make_config("1", **{"track_cfg/guard/lost_below": 0.5, "track_cfg/guard/yaxis_only": True}))
+    from captra_amd import track_options
+    g = track_options.guard_cfg(make_config("1", **{"track_cfg/guard/lost_below": 0.5, "track_cfg/guard/yaxis_only": True}))
     assert g["yaxis_only"] is True
     for off in ({}, {"track_cfg/guard/yaxis_only": False}):
-        g = EvalTrackModel._guard_cfg(make_config("1", **{"track_cfg/guard/lost_below": 0.5, **off}))
+        g = track_options.guard_cfg(make_config("1", **{"track_cfg/guard/lost_below": 0.5, **off}))
         assert set(g) == {"refit", "lost_below", "inlier_th", "min_members", "num_hyps", "seed"}
 
 

@@ -1,5 +1,5 @@
 """The configuration surface of init_frame/image_fit (the first pose fitted from frame 0's depth, mask and NOCS coordinate image):
-the flags, EvalTrackModel._image_fit_cfg and every error it raises, the error of a frame 0 without its images, the optional `coord`
+the flags, track_options.image_fit_cfg and every error it raises, the error of a frame 0 without its images, the optional `coord`
 array of the trajectory files, synthetic's `coord` (default = the shipped frames, byte for byte), the table of captra_amd.eval and the
 binding row."""
 import argparse
@@ -52,11 +52,11 @@ def test_parse_args_builds_the_option():
 
 def test_absent_option_is_none_and_defaults():
     from captra_amd.configs import make_config
-    from captra_amd.model import EvalTrackModel
-    assert EvalTrackModel._image_fit_cfg(make_config("1")) is None
-    assert EvalTrackModel._image_fit_cfg(_cfg(image_fit=False, border=9)) is None     # off: nothing is looked at
-    assert EvalTrackModel._image_fit_cfg(_cfg(image_fit=True)) == {"cap": 16384, "border": 0, "negate_z": False}
-    assert EvalTrackModel._image_fit_cfg(_cfg(image_fit=True, border=3, cap=3, coord_negate_z=True)) == {"cap": 3, "border": 3, "negate_z": True}
+    from captra_amd import track_options
+    assert track_options.image_fit_cfg(make_config("1")) is None
+    assert track_options.image_fit_cfg(_cfg(image_fit=False, border=9)) is None     # off: nothing is looked at
+    assert track_options.image_fit_cfg(_cfg(image_fit=True)) == {"cap": 16384, "border": 0, "negate_z": False}
+    assert track_options.image_fit_cfg(_cfg(image_fit=True, border=3, cap=3, coord_negate_z=True)) == {"cap": 3, "border": 3, "negate_z": True}
 
 
 @pytest.mark.parametrize("section,word", [
@@ -65,20 +65,20 @@ def test_absent_option_is_none_and_defaults():
     (dict(border=-1), "init_frame/border"), (dict(border=4), "init_frame/border"), (dict(border=1.5), "init_frame/border"),
 ])
 def test_errors_of_the_option(section, word):
-    from captra_amd.model import EvalTrackModel
+    from captra_amd import track_options
     with pytest.raises(ValueError, match=word):
-        EvalTrackModel._image_fit_cfg(_cfg(image_fit=True, **section))
+        track_options.image_fit_cfg(_cfg(image_fit=True, **section))
 
 
 def test_an_articulated_object_is_refused():
     from captra_amd.configs import make_config
-    from captra_amd.model import EvalTrackModel
+    from captra_amd import track_options
     from captra_amd.synthetic import PHYSICAL_SETUPS
     cat, objcfg = PHYSICAL_SETUPS["drawers"][:2]
     cfg = make_config(cat, objcfg, **{"init_frame/image_fit": True})
     assert int(cfg["num_parts"]) > 1
     with pytest.raises(ValueError, match="num_parts"):
-        EvalTrackModel._image_fit_cfg(cfg)
+        track_options.image_fit_cfg(cfg)
 
 
 def test_the_model_parses_the_option_and_asks_for_frame_0s_images():

@@ -128,7 +128,7 @@ def test_judge_chain_recovers_the_synthetic_pose():
     factor covers a later change of num_hyps."""
     from captra_amd import synthetic as S
     from captra_amd.configs import make_config
-    from captra_amd.model import INIT_FIT_INLIER_TH
+    from captra_amd.track_options import INIT_FIT_INLIER_TH
     th = INIT_FIT_INLIER_TH * float(make_config("1")["data_radius"])
     kinv = IJ.kinv_of(IJ.NOCS_INTRINSICS["real"])
     for seed in MEASURED:

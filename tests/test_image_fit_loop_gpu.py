@@ -75,7 +75,7 @@ def _by_hand(model):
 
 
 def test_first_pose_is_the_chain_by_hand_and_the_judges(trainers, data, eager_on):
-    from captra_amd.model import INIT_FIT_INLIER_TH
+    from captra_amd.track_options import INIT_FIT_INLIER_TH
     model = trainers["on"].model
     poses, pred = eager_on
     mem, (rot, scale, trans, valid, info) = _by_hand(model)

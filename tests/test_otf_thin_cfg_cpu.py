@@ -1,5 +1,5 @@
 """The configuration surface of track_cfg/otf_thin (the re-crop's lists thinned on the device): the flags, the shipped default,
-EvalTrackModel._otf_thin_cfg, the table of captra_amd.eval, the binding rows, and synthetic's blob_px (default = the shipped frames)."""
+track_options.otf_thin_cfg, the table of captra_amd.eval, the binding rows, and synthetic's blob_px (default = the shipped frames)."""
 import argparse
 
 import numpy as np
@@ -20,16 +20,16 @@ def test_parse_args_builds_the_otf_thin_cfg():
 
 def test_otf_thin_cfg_defaults_and_errors():
     from captra_amd.configs import make_config
-    from captra_amd.model import EvalTrackModel
-    assert EvalTrackModel._otf_thin_cfg(make_config("1")) is None
-    assert EvalTrackModel._otf_thin_cfg(make_config("1", **{"track_cfg/otf_thin/seed": 5})) is None
-    assert EvalTrackModel._otf_thin_cfg(make_config("1", **{"track_cfg/otf_thin/device": True})) == {"seed": 0}
-    assert EvalTrackModel._otf_thin_cfg(make_config("1", **{"track_cfg/otf_thin/device": True, "track_cfg/otf_thin/seed": 5})) == {"seed": 5}
+    from captra_amd import track_options
+    assert track_options.otf_thin_cfg(make_config("1")) is None
+    assert track_options.otf_thin_cfg(make_config("1", **{"track_cfg/otf_thin/seed": 5})) is None
+    assert track_options.otf_thin_cfg(make_config("1", **{"track_cfg/otf_thin/device": True})) == {"seed": 0}
+    assert track_options.otf_thin_cfg(make_config("1", **{"track_cfg/otf_thin/device": True, "track_cfg/otf_thin/seed": 5})) == {"seed": 5}
     cfg = make_config("1")
     del cfg["track_cfg"]["otf_thin"]
-    assert EvalTrackModel._otf_thin_cfg(cfg) is None
+    assert track_options.otf_thin_cfg(cfg) is None
     with pytest.raises(ValueError, match="seed"):
-        EvalTrackModel._otf_thin_cfg(make_config("1", **{"track_cfg/otf_thin/device": True, "track_cfg/otf_thin/seed": -1}))
+        track_options.otf_thin_cfg(make_config("1", **{"track_cfg/otf_thin/device": True, "track_cfg/otf_thin/seed": -1}))
 
 
 def test_eval_lists_the_frames_thinned():

@@ -232,7 +232,7 @@ def test_initial_pose_fitted_from_frame0(device, tag):
     """init_frame: {gt: False, fit: True} at B = 2: the synthetic NOCS map is exact, every member is an inlier and the fit is
     the full-cloud Umeyama -- the float64 judge is within 1e-4 of frame 0's nocs2camera, and the model's first pose is within
     the kernel's bounds of the judge (hence needs no annotation: the fallback it was given is a perturbed pose)."""
-    from captra_amd.model import INIT_FIT_INLIER_TH
+    from captra_amd.track_options import INIT_FIT_INLIER_TH
     trainer, cfg, data = _model(tag, device, {"gt": False, "fit": True}, frames=1)
     model = trainer.model
     model.set_data(data)

@@ -91,21 +91,21 @@ def test_parse_args_builds_the_rot_pool_cfg():
 
 def test_rot_pool_cfg_defaults_and_errors():
     from captra_amd.configs import make_config
-    from captra_amd.model import EvalTrackModel
-    assert EvalTrackModel._rot_pool_cfg(make_config("1")) is None
-    assert EvalTrackModel._rot_pool_cfg(make_config("1", **{"track_cfg/rot_pool/consensus": False, "track_cfg/rot_pool/num_hyps": 0})) is None
+    from captra_amd import track_options
+    assert track_options.rot_pool_cfg(make_config("1")) is None
+    assert track_options.rot_pool_cfg(make_config("1", **{"track_cfg/rot_pool/consensus": False, "track_cfg/rot_pool/num_hyps": 0})) is None
     on = {"track_cfg/rot_pool/consensus": True, "track_cfg/rot_pool/angle_th": 15.0}
-    assert EvalTrackModel._rot_pool_cfg(make_config("1", **on)) == {"angle_th": 15.0, "num_hyps": 64, "seed": 0}
+    assert track_options.rot_pool_cfg(make_config("1", **on)) == {"angle_th": 15.0, "num_hyps": 64, "seed": 0}
     cfg = make_config("1", **on, **{"init_frame/num_hyps": 48, "init_frame/seed": 9})
-    assert EvalTrackModel._rot_pool_cfg(cfg) == {"angle_th": 15.0, "num_hyps": 48, "seed": 9}
+    assert track_options.rot_pool_cfg(cfg) == {"angle_th": 15.0, "num_hyps": 48, "seed": 9}
     cfg = make_config("1", **on, **{"track_cfg/rot_pool/num_hyps": 32, "track_cfg/rot_pool/seed": 3})
-    assert EvalTrackModel._rot_pool_cfg(cfg) == {"angle_th": 15.0, "num_hyps": 32, "seed": 3}
+    assert track_options.rot_pool_cfg(cfg) == {"angle_th": 15.0, "num_hyps": 32, "seed": 3}
     with pytest.raises(ValueError, match="angle_th"):          # no default
-        EvalTrackModel._rot_pool_cfg(make_config("1", **{"track_cfg/rot_pool/consensus": True}))
+        track_options.rot_pool_cfg(make_config("1", **{"track_cfg/rot_pool/consensus": True}))
     for key, bad in (("angle_th", 0.0), ("angle_th", -5.0), ("angle_th", 180.0), ("angle_th", float("nan")), ("num_hyps", 0), ("num_hyps", 257),
                      ("seed", -1)):
         with pytest.raises(ValueError, match=key):
-            EvalTrackModel._rot_pool_cfg(make_config("1", **{**on, f"track_cfg/rot_pool/{key}": bad}))
+            track_options.rot_pool_cfg(make_config("1", **{**on, f"track_cfg/rot_pool/{key}": bad}))
     from captra_amd.trainer import Trainer
     with pytest.raises(ValueError, match="angle_th"):
         Trainer(make_config("1", experiment_dir="/tmp/captra_test_exp", **{"track_cfg/rot_pool/consensus": True}))

@@ -1,6 +1,6 @@
 """CPU: the float64 judge of the robust scale / translation fit (tests/st_ransac_judge.py) -- its estimator pinned to the oracle's
 one-pass fit, what it is for (outliers), its in-plane invariance -- and the configuration surface of track_cfg/st_fit: flags,
-EvalTrackModel._st_fit_cfg, the table of captra_amd.eval."""
+track_options.st_fit_cfg, the table of captra_amd.eval."""
 import argparse
 import pickle
 import re
@@ -113,19 +113,20 @@ def test_parse_args_builds_the_st_fit_cfg():
 
 def test_st_fit_cfg_defaults_and_errors():
     from captra_amd.configs import make_config
-    from captra_amd.model import INIT_FIT_INLIER_TH, EvalTrackModel
-    assert EvalTrackModel._st_fit_cfg(make_config("1")) is None
-    assert EvalTrackModel._st_fit_cfg(make_config("1", **{"track_cfg/st_fit/ransac": False, "track_cfg/st_fit/num_hyps": 0})) is None
+    from captra_amd import track_options
+    from captra_amd.track_options import INIT_FIT_INLIER_TH
+    assert track_options.st_fit_cfg(make_config("1")) is None
+    assert track_options.st_fit_cfg(make_config("1", **{"track_cfg/st_fit/ransac": False, "track_cfg/st_fit/num_hyps": 0})) is None
     cfg = make_config("1", **{"track_cfg/st_fit/ransac": True})
-    assert EvalTrackModel._st_fit_cfg(cfg) == {"inlier_th": INIT_FIT_INLIER_TH * cfg["data_radius"], "num_hyps": 64, "seed": 0}
+    assert track_options.st_fit_cfg(cfg) == {"inlier_th": INIT_FIT_INLIER_TH * cfg["data_radius"], "num_hyps": 64, "seed": 0}
     cfg = make_config("1", **{"track_cfg/st_fit/ransac": True, "init_frame/num_hyps": 48, "init_frame/seed": 9})
-    assert EvalTrackModel._st_fit_cfg(cfg) == {"inlier_th": INIT_FIT_INLIER_TH * cfg["data_radius"], "num_hyps": 48, "seed": 9}
+    assert track_options.st_fit_cfg(cfg) == {"inlier_th": INIT_FIT_INLIER_TH * cfg["data_radius"], "num_hyps": 48, "seed": 9}
     cfg = make_config("1", **{"track_cfg/st_fit/ransac": True, "track_cfg/st_fit/inlier_th": 0.01, "track_cfg/st_fit/num_hyps": 32,
                               "track_cfg/st_fit/seed": 3})
-    assert EvalTrackModel._st_fit_cfg(cfg) == {"inlier_th": 0.01 * cfg["data_radius"], "num_hyps": 32, "seed": 3}
+    assert track_options.st_fit_cfg(cfg) == {"inlier_th": 0.01 * cfg["data_radius"], "num_hyps": 32, "seed": 3}
     for key, bad in (("inlier_th", 0.0), ("inlier_th", -0.01), ("num_hyps", 0), ("num_hyps", -4), ("num_hyps", 257), ("seed", -1)):
         with pytest.raises(ValueError, match=key):
-            EvalTrackModel._st_fit_cfg(make_config("1", **{"track_cfg/st_fit/ransac": True, f"track_cfg/st_fit/{key}": bad}))
+            track_options.st_fit_cfg(make_config("1", **{"track_cfg/st_fit/ransac": True, f"track_cfg/st_fit/{key}": bad}))
     from captra_amd.trainer import Trainer
     with pytest.raises(ValueError, match="num_hyps"):
         Trainer(make_config("1", experiment_dir="/tmp/captra_test_exp", **{"track_cfg/st_fit/ransac": True, "track_cfg/st_fit/num_hyps": 0}))
