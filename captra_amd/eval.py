@@ -131,6 +131,20 @@ def rot_pool_table(name: str, data: dict) -> list:
     return lines
 
 
+def motion_table(name: str, data: dict) -> list:
+    """The motion model's record of one result pickle (present when the run had track_cfg/motion/predict): one line per part with the
+    frames whose start pose was predicted (`used`: the NEXT frame started from an extrapolation) and the largest step the history
+    saw, in degrees and in the translation's units."""
+    frames = [(np.asarray(r["used"]).reshape(-1), np.asarray(r["angle"]).reshape(-1), np.asarray(r["shift"]).reshape(-1))
+              for r in data["motion"] if r is not None and "used" in r]
+    lines = []
+    for p in range(len(frames[0][0]) if frames else 0):
+        used = sum(1 for u, _, _ in frames if int(u[p]) != 0)
+        lines.append(f"{name} part {p}: predicted {used} / {len(frames)} frames; largest step {max(float(a[p]) for _, a, _ in frames):.2f} deg, "
+                     f"{max(float(s[p]) for _, _, s in frames):.4f}")
+    return lines
+
+
 def otf_thin_table(name: str, data: dict) -> list:
     """The re-crop's on-device thinning record of one result pickle (present when the run had track_cfg/otf_thin/device): one line
     with the frames whose candidate list was thinned, of the frames re-cropped."""
@@ -160,6 +174,7 @@ RECORD_TABLES = (
     ("guard", guard_table, "track guard ({tests} inlier test), frames per trajectory and part:"),
     ("st_fit", st_fit_table, "robust scale / translation fit (track_cfg/st_fit), frames per trajectory and part:"),
     ("rot_pool", rot_pool_table, "consensus rotation read-out (track_cfg/rot_pool), per trajectory and part:"),
+    ("motion", motion_table, "constant-velocity start pose (track_cfg/motion), per trajectory and part:"),
     ("otf_thin", otf_thin_table, "re-crop lists thinned on the device (track_cfg/otf_thin), frames per trajectory:"),
     ("depth_filter", depth_filter_table, "flying depth pixels removed at upload (track_cfg/depth_filter), per trajectory:"),
     ("image_fit", image_fit_table, "first pose fitted from frame 0's images (init_frame/image_fit), per trajectory:"),

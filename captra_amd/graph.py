@@ -66,6 +66,9 @@ class TrackStepGraph:
         # a LANE of a larger batch (TrackLanes) must compute what the whole batch computes: the few-trajectory split-k rule of
         # EvalTrackModel._step_context goes by the batch it sees, so it is switched off for sub-batches
         self.allow_split_k = allow_split_k
+        if getattr(model, "motion", None) is not None:
+            from .track_options import entering_pose
+            pose = entering_pose(pose)          # track_cfg/motion: the captured buffers hold the travelling dict, prediction included
         self.b0 = int(b0)          # a lane's first trajectory within the whole batch: the track guard draws by it (a launch argument, captured)
         dev = points.device
         self.points = points.clone()
@@ -181,6 +184,9 @@ class TrackStepGraph:
                                "capture a new TrackStepGraph")
         pairs = [(points, self.points), (points_mean, self.points_mean)]
         if pose is not self.pose:          # (a lane of TrackLanes hands its pose over in place)
+            if len(pose) < len(self.pose):
+                from .track_options import entering_pose
+                pose = entering_pose(pose)      # track_cfg/motion: a dict without a prediction is a track's start
             pairs += [(pose[k], self.pose[k]) for k in self.pose]
         if self.labels is not None and labels is not None:
             pairs.append((labels, self.labels))
@@ -217,6 +223,8 @@ class TrackLanes:
         B = points.shape[0]
         if lanes < 1 or B % lanes:
             raise ValueError(f"{B} trajectories do not split into {lanes} lanes")
+        self.motion = getattr(model, "motion", None) is not None
+        pose = self._entering(pose)
         dev = points.device
         per = B // lanes
         self.slices = [slice(l * per, (l + 1) * per) for l in range(lanes)]
@@ -238,9 +246,17 @@ class TrackLanes:
     def stale(self) -> bool:
         return any(g.stale() for g in self.graphs)
 
+    def _entering(self, pose: dict) -> dict:
+        """track_cfg/motion: the travelling dict (track_options.entering_pose); else `pose` itself."""
+        if not self.motion:
+            return pose
+        from .track_options import entering_pose
+        return entering_pose(pose)
+
     def set_pose(self, pose: dict) -> None:
         """(Re)start the trajectories from `pose` (B-major dict) — the initial pose of the track loop (model.py:394)."""
         cur = torch.cuda.current_stream()
+        pose = self._entering(pose)
         for g, s, st in zip(self.graphs, self.slices, self.streams):
             st.wait_stream(cur)
             with torch.cuda.stream(st):
@@ -267,7 +283,7 @@ class TrackLanes:
                 if self.npcs_ring is not None:
                     pairs += [(g.npcs_pred[k], dst[s]) for k, dst in self.npcs_ring[slot].items()]
                 # (6 pose + 3 map jobs, 4 more with a guard record, 2 with the robust fit's: 15, within the launch's 16; the consensus
-                # read-out's 2 on top of all of them take a second launch)
+                # read-out's 2 on top of all of them take a second launch, and so do the motion model's 6 pose + 5 record jobs)
                 for j in range(0, len(pairs), 16):
                     fused.copy_multi(pairs[j:j + 16])
                 self.written[slot][l].record(st)

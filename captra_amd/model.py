@@ -128,6 +128,7 @@ class EvalTrackModel(BaseModel):
         self._warn_full_rotation_test(cfg)
         self.st_fit = self.net.st_fit = O.st_fit_cfg(cfg)                  # every step's scale / translation by RANSAC
         self.rot_pool = self.net.rot_pool = O.rot_pool_cfg(cfg)            # every step's rotation from the votes' consensus
+        self.motion = O.motion_cfg(cfg)                                    # every step starts from a constant-velocity prediction
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
         self.otf_thin = O.otf_thin_cfg(cfg)                                # the re-crop's over-long lists thinned on the device
         self._otf_thin_rec = {}             # frame -> {first trajectory of a slice: its thinned flags (b,) int32 on the device}
@@ -318,8 +319,12 @@ class EvalTrackModel(BaseModel):
                 yield
 
     def track_step(self, input, npcs_input, last_pose, allow_split_k=True):
-        """One frame for all B trajectories: CoordNet -> labels -> RotationNet -> pose fit [-> guard].  input['b0']: the index
-        of the first trajectory within the whole batch when `input` is a lane of one (the guard's draws; default 0)."""
+        """One frame for all B trajectories: CoordNet -> labels -> RotationNet -> pose fit [-> guard] [-> motion model].  input['b0']: the index
+        of the first trajectory within the whole batch when `input` is a lane of one (the guard's draws; default 0).
+        track_cfg/motion: `last_pose` carries the prediction the step starts from (a dict without one is a track's start) and the
+        returned dict the next one; the four phases take the dict as it travels and read their start pose out of it."""
+        if self.motion is not None:
+            last_pose = O.entering_pose(last_pose)
         with self._step_context(input["points"], allow_split_k):
             self._step_begin(input, npcs_input, last_pose)
             join = self._fork_rotation_net(input, npcs_input, last_pose) if self._overlap_nets(input) else None
@@ -335,6 +340,7 @@ class EvalTrackModel(BaseModel):
     # ---- the step in four phases (what `track_step` composes; captra_amd.graph.TrackStepGraph(split=True) captures each as a
     # hipGraph of its own and replays [prep] -> [rot || coord] -> [post] on two EXPLICIT streams) ---------------------------
     def _step_begin(self, input, npcs_input, last_pose):
+        last_pose = O.start_pose(last_pose)
         # (a view when it is contiguous -- one part: the clones are three copy kernels per step and nothing writes into them)
         npcs_input["canon_pose"] = {k: (v if v.is_contiguous() else v.clone()) for k, v in
                                     ((k, last_pose[k][:, self.root]) for k in ("rotation", "translation", "scale"))}
@@ -399,6 +405,7 @@ class EvalTrackModel(BaseModel):
     def _step_rot(self, input, npcs_input, last_pose):
         """RotationNet up to its heads' raw per-point output (needs nothing of CoordinateNet's but, for one part, its geometry)."""
         P = self.num_parts
+        last_pose = O.start_pose(last_pose)
         cam, geom = npcs_input["_canon"], npcs_input["_geom"]
         if P == 1 and self.share_geometry:            # one part: RotationNet's cloud IS CoordinateNet's
             return self.net.regress_net.raw_point_rtvec(cam[0], cam_n3=cam[1], geom=geom)
@@ -411,6 +418,7 @@ class EvalTrackModel(BaseModel):
         return self.npcs_net(npcs_input)
 
     def _step_post(self, input, npcs_input, npcs_pred, last_pose):
+        entered, last_pose = last_pose, O.start_pose(last_pose)
         pred_npcs = npcs_pred["nocs"].reshape(len(npcs_pred["nocs"]), self.num_parts, 3, -1)
         input["state"] = {"part": last_pose}
         lab32 = npcs_pred.pop("_labels_i32", None)   # CoordinateNet's fused read-out: the int32 labels of THIS prediction
@@ -433,7 +441,23 @@ class EvalTrackModel(BaseModel):
             if getattr(self, name) is not None:
                 # the option's record joins CoordinateNet's maps (`st_*`, `rot_*`), so it travels with them through every batch form
                 O.put_record(npcs_pred, name, out[name])
-        return pose if self.guard is None else self._guard_step(input, npcs_pred, pose)
+        if self.guard is not None:
+            pose = self._guard_step(input, npcs_pred, pose)
+        return pose if self.motion is None else self._motion_step(npcs_pred, entered, pose)
+
+    def _motion_step(self, npcs_pred, entered, pose):
+        """The motion model behind the fit and the guard: the pose the NEXT step starts from, out of the result that entered this
+        step (`entered`: rotation / translation / measured) and this step's; its record joins CoordinateNet's maps (`motion_*`);
+        -> the step's pose with next_rotation / next_translation / measured beside its three keys."""
+        from .pose_utils.pose_fit import pose_extrapolate
+        m = self.motion
+        verdict = npcs_pred["guard_verdict"] if self.guard is not None else None
+        rot, trans, measured, info = pose_extrapolate(entered["rotation"], entered["translation"], pose["rotation"], pose["translation"],
+                                                      entered["measured"], bool(self.sym), m["max_angle"], m["max_shift"], gain=m["gain"],
+                                                      verdict=verdict)
+        O.put_record(npcs_pred, "motion", {**info, "rotation": rot, "translation": trans})
+        return {"rotation": pose["rotation"], "scale": pose["scale"], "translation": pose["translation"],
+                "next_rotation": rot, "next_translation": trans, "measured": measured}
 
     def _guard_step(self, input, npcs_pred, pose):
         """The guard behind the pose fit, on the labels the fit used; its record joins CoordinateNet's maps (`guard_*`), so it
@@ -525,6 +549,7 @@ class EvalTrackModel(BaseModel):
         that one away too (nocs_otf.full_data_batch_arrays) and appends the device word [rare-path instance met, longest list] to
         the result -- the caller reads it a frame late (_OtfCheck) and runs the frame again without `defer` when it is set."""
         from .nocs_otf import full_data_batch_arrays, to_host
+        last_pose = O.start_pose(last_pose)        # (track_cfg/motion: the crop follows the prediction)
         pre = input.get("pre_fetched")
         if pre is None:
             raise ValueError("nocs_otf=True needs the frame's depth and mask tensors (meta['pre_fetched']): reading depth.png / "
@@ -759,7 +784,8 @@ class EvalTrackModel(BaseModel):
             else:
                 frames = self._batch_frames
             with torch.no_grad():
-                run_frame, commit, poses, bounds, join = frames(pred_poses[0])
+                # (track_cfg/motion: the travelling dict carries the prediction beside the pose; frame 0's is a track's start)
+                run_frame, commit, poses, bounds, join = frames(pred_poses[0] if self.motion is None else O.entering_pose(pred_poses[0]))
                 commit = O.commit_with_records(commit, records)
                 pending = None                  # (frame, poses that entered it, its deferred checks)
 

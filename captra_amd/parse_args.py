@@ -46,6 +46,10 @@ _FLAGS = [  # (name, type, default)
     # given, and then abs_mm (millimetres) and min_support are required
     ("track_cfg/depth_filter/window", int, None), ("track_cfg/depth_filter/abs_mm", int, None),
     ("track_cfg/depth_filter/rel_permille", int, None), ("track_cfg/depth_filter/min_support", int, None),
+    # every step starts from a constant-velocity prediction (track_options.py: motion_cfg); off unless predict is True, and then max_angle
+    # (degrees) and max_shift (a fraction of data_radius) are required
+    ("track_cfg/motion/predict", boolean_string, None), ("track_cfg/motion/max_angle", float, None),
+    ("track_cfg/motion/max_shift", float, None), ("track_cfg/motion/gain", float, None),
     # optimisation
     ("total_epoch", int, None), ("optimizer", str, None), ("weight_decay", float, None), ("learning_rate", float, None),
     ("lr_policy", str, None), ("lr_gamma", float, None), ("lr_step_size", int, None), ("lr_clip", float, None), ("freq/save", int, None),

@@ -216,3 +216,30 @@ def part_fit_guard_cn(labels_i32, src_cn, pts_cn, pts_mean, pose, inlier_th, los
     if not refit:
         return pose, info
     return {"rotation": out[0], "scale": out[1], "translation": out[2].unsqueeze(-1)}, info
+
+
+def pose_extrapolate(rot0, trans0, rot1, trans1, measured0, sym: bool, max_angle, max_shift, gain=1.0, verdict=None):
+    """The motion model in one launch (captra_pose_extrapolate, include/captra_hip.h): rot0 (B,P,3,3), trans0 (B,P,3[,1]) = the result
+    of the frame before, rot1 / trans1 = this frame's result, measured0 (B,P) int32 (nonzero: rot0 / trans0 are a measured result),
+    verdict (B,P) int32 = the guard's codes of this frame (GUARD_VERDICTS) or None (all ok); max_angle in degrees inside (0, 90],
+    max_shift in the translation's units, gain inside (0, 1]; sym: only the y-axis of a symmetric category moves.
+    -> (rot_next (B,P,3,3), trans_next (B,P,3,1) = the pose the next frame starts from, measured1 (B,P) int32,
+        info {'used' (B,P) int32, 'angle' (B,P) float32 degrees, 'shift' (B,P) float32})."""
+    B, P = rot0.shape[:2]
+    dev = rot0.device
+    rot0, rot1 = rot0.float().contiguous(), rot1.float().contiguous()
+    trans0, trans1 = trans0.reshape(B, P, 3).float().contiguous(), trans1.reshape(B, P, 3).float().contiguous()
+    measured0 = measured0.int().contiguous()
+    if verdict is not None:
+        verdict = verdict.int().contiguous()
+    L.require_device(rot0, trans0, rot1, trans1, measured0, verdict)
+    rot_next, trans_next = torch.empty_like(rot1), torch.empty_like(trans1)
+    measured1 = torch.empty(B, P, dtype=torch.int32, device=dev)
+    used = torch.empty(B, P, dtype=torch.int32, device=dev)
+    angle = torch.empty(B, P, dtype=torch.float32, device=dev)
+    shift = torch.empty(B, P, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("captra_pose_extrapolate", B, P, 1 if sym else 0, L.ptr(rot0), L.ptr(trans0), L.ptr(rot1), L.ptr(trans1), L.ptr(measured0),
+               L.ptr(verdict), float(gain), float(max_angle), float(max_shift), L.ptr(rot_next), L.ptr(trans_next), L.ptr(measured1),
+               L.ptr(used), L.ptr(angle), L.ptr(shift))
+    return rot_next, trans_next.unsqueeze(-1), measured1, {"used": used, "angle": angle, "shift": shift}

@@ -156,11 +156,62 @@ def depth_filter_cfg(cfg):
     return dict(zip(("window", "abs_mm", "rel_permille", "min_support"), vals))
 
 
+def motion_cfg(cfg):
+    """track_cfg: {motion: {predict: True, max_angle: <degrees>, max_shift: <fraction of data_radius>, gain: 1.0}}: every step STARTS
+    from a constant-velocity prediction instead of the pose the step before produced (csrc/pose_motion.hip, include/captra_hip.h:
+    captra_pose_extrapolate -- one launch behind the fit and the guard, captured with the step): the re-crop's centre, both networks'
+    canonicalisation, R_prev of the read-out and what an invalid fit keeps.  The prediction travels in the pose dict (next_rotation,
+    next_translation, measured) and is recorded per frame (pred_dict / pickle 'motion').  None when absent or predict is not set;
+    max_angle and max_shift have no default -- they depend on the frame rate and on how fast the objects move: a step larger than
+    either is a glitch in the history, not a velocity --, max_shift is a fraction of data_radius, gain defaults to 1."""
+    m = cfg["track_cfg"].get("motion")
+    if m is None or not m.get("predict", False):
+        return None
+    vals = {}
+    for key, lo_open, hi, what in (("max_angle", 0.0, 90.0, "an angle in degrees inside (0, 90]"),
+                                   ("max_shift", 0.0, np.inf, "a positive fraction of data_radius"), ("gain", 0.0, 1.0, "inside (0, 1]")):
+        v = m.get(key)
+        if v is None and key == "gain":
+            v = 1.0
+        if v is None:
+            raise ValueError(f"track_cfg/motion/predict needs track_cfg/motion/{key} ({what}): it has no default")
+        v = float(v)
+        if not (lo_open < v <= hi and np.isfinite(v)):
+            raise ValueError(f"track_cfg/motion/{key} must be {what}, got {m.get(key)!r}")
+        vals[key] = v
+    vals["max_shift"] *= float(cfg["data_radius"])
+    return vals
+
+
+# The pose dict that travels from frame to frame: these three, and with track_cfg/motion three more -- the pose the next step starts
+# from and whether the dict's own pose is a measured result (a track's start is not).  The dict is the loop's whole state.
+POSE_KEYS = ("rotation", "scale", "translation")
+
+
+def entering_pose(pose):
+    """track_cfg/motion: a dict with only the three keys is a track's START -- the prediction is the pose itself and nothing is
+    measured yet, so frame 1 never extrapolates.  A dict that carries its prediction passes through."""
+    if "next_rotation" in pose:
+        return pose
+    import torch
+    return {**pose, "next_rotation": pose["rotation"], "next_translation": pose["translation"],
+            "measured": torch.zeros(pose["scale"].shape, dtype=torch.int32, device=pose["scale"].device)}
+
+
+def start_pose(pose):
+    """The pose a step starts from: the prediction where the dict carries one (scale has no velocity), else the dict itself."""
+    if "next_rotation" not in pose:
+        return pose
+    return {"rotation": pose["next_rotation"], "scale": pose["scale"], "translation": pose["next_translation"]}
+
+
 # ---- the records: name in pred_dict and the pickle (and of the model attribute that switches the option on) -> ... ---------------
 # A step's records, (B,P) tensors per frame -> (the prefix its keys travel under inside CoordinateNet's maps, the keys)
 STEP_RECORDS = {"guard": ("guard_", ("count", "inliers", "rms", "verdict")),     # pose_utils/pose_fit.py
                 "st_fit": ("st_", ("inliers", "valid")),                         # int32
-                "rot_pool": ("rot_", ("inliers", "count"))}                      # int32
+                "rot_pool": ("rot_", ("inliers", "count")),                      # int32
+                # used int32, angle (degrees) / shift float32, and the predicted pose itself: (B,P,3,3), (B,P,3,1)
+                "motion": ("motion_", ("used", "angle", "shift", "rotation", "translation"))}
 # The host loop's records, ONE (B,) int32 tensor per frame (None: a frame without) -> the key that wraps it in the pickle.
 # otf_thin: which trajectories' lists were thinned (its sum: the frame's thinned instances); depth_filter: the pixels set to 0
 LOOP_RECORDS = {"otf_thin": "thinned", "depth_filter": "removed"}
@@ -181,6 +232,8 @@ def commit_with_records(commit, records):
         for name, frames in records.items():
             prefix, keys = STEP_RECORDS[name]
             frames[i] = {k: npcs.pop(prefix + k) for k in keys}
+        if "motion" in records:
+            pose = {k: pose[k] for k in POSE_KEYS}      # a committed frame keeps the three keys; the prediction is in its record
         return npcs, pose
     return wrapped if records else commit
 

@@ -940,6 +940,38 @@ int captra_rot_pool_consensus(int b, int p, int n, int sym, int diag_only, int b
                               const int *labels, const float *prev_rot, const int *sample_rank, unsigned long long seed, float *rot,
                               float *delta, int *count, int *num_inliers, int *best, captra_stream_t stream);
 
+/* Motion model (no reference counterpart: its frame i+1 starts from the result of frame i): the pose frame i+1 STARTS from, by
+ * constant velocity from the results of frames i-1 and i.  One launch, one thread per (trajectory, part), B * P threads in 64-lane
+ * workgroups; no atomics, no LDS.  All arithmetic in double on the fp32 inputs as stored, every output rounded to fp32 once; the
+ * gates compare the doubles.  b < 1, 9 B P beyond INT_MAX, P outside [1, 8], sym outside {0, 1}, gain outside (0, 1], max_angle_deg outside (0, 90],
+ * max_shift not positive and finite (a NaN of any of the three included), or a NULL among the pointers other than verdict return -1
+ * without a launch.
+ *   rot0 (B,P,3,3), trans0 (B,P,3): the result of the frame before; rot1, trans1: this frame's result; measured0 (B,P) i32: nonzero =
+ *   rot0 / trans0 are a measured result (0: a track's first pose, or a pose that only passed through a lost frame); verdict (B,P) i32:
+ *   the codes of captra_part_fit_guard for THIS frame (0 ok, 1 too_few, 2 lost, 3 recovered), NULL = all 0.
+ *   finite   : all 24 input floats of (b, p) are finite.
+ *   shift    : |trans1 - trans0|, in the translation's units.
+ *   angle    : the step's angle theta in degrees, theta = atan2(|v|, c) with
+ *              sym = 0: D = rot1 rot0^T, v = (D[2][1] - D[1][2], D[0][2] - D[2][0], D[1][0] - D[0][1]) / 2, c = (tr D - 1) / 2;
+ *              sym = 1: a symmetric category's in-plane angle carries no information (see the axis-only test above), so only the axis
+ *                       moves: a_k = the second column of rot_k, v = a0 x a1, c = a0 . a1.
+ *   measured1 (B,P) i32 = finite && verdict in {0, 3}: a re-fitted pose is a measurement and starts a new history; a part that is lost
+ *              or has too few members is none.
+ *   used     (B,P) i32 = measured0 != 0 && finite && verdict == 0 && angle <= max_angle_deg && shift <= max_shift (a step larger than
+ *              either is a glitch in the history, not a velocity).
+ *   used     : trans_next = fp32(trans1 + gain (trans1 - trans0)); rot_next = fp32(Q rot1), Q = I + sin(phi) K + (1 - cos(phi)) K^2,
+ *              phi = gain * theta, K the cross-product matrix of v / |v|.  With |v| == 0 exactly -- which bit-equal rotations give --
+ *              the rotation part is rot1, bit for bit.
+ *   not used : rot_next, trans_next = rot1, trans1, bit for bit, non-finite values included: the pass-through never invents a value.
+ *   angle, shift (B,P) f32 are always written, 0 when not finite: no NaN leaves the kernel through them.
+ * The scale is not extrapolated: a rigid part's scale has no velocity.  max_angle_deg stops at 90 degrees because the axis is read
+ * from the antisymmetric part of D, which is well conditioned away from 180 degrees; the kernel never extrapolates beyond.
+ * Outputs must not alias inputs. */
+int captra_pose_extrapolate(int b, int p, int sym, const float *rot0, const float *trans0, const float *rot1, const float *trans1,
+                            const int *measured0, const int *verdict, float gain, float max_angle_deg, float max_shift,
+                            float *rot_next, float *trans_next, int *measured1, int *used, float *angle, float *shift,
+                            captra_stream_t stream);
+
 /* Batched 3x3 orthogonal Procrustes: R = U diag(1,1,det(U V^T)) V^T with U S V^T = tgt^T src
  * (rotate_pts_batch procrustes.py:25-56).  src, tgt (nb,N,3) -> rot (nb,3,3).  One-sided Jacobi. */
 int captra_procrustes_rot3(int nb, int n, const float *src, const float *tgt, float *rot,
