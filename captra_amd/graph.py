@@ -10,6 +10,7 @@ The reference has no equivalent (eager PyTorch, one ATen launch at a time, model
 from __future__ import annotations
 
 import os
+import weakref
 
 import torch
 
@@ -61,7 +62,10 @@ class TrackStepGraph:
         """model: EvalTrackModel (eval mode, on the GPU); points (B,3,N), points_mean (B,3,1), pose: example inputs.
         split_side: a stream -> the step is captured as four linear graphs and its RotationNet branch replays on that stream
         (see SPLIT_OTF_LANES); None -> one graph, the networks as its two branches when model.overlap_nets."""
-        self.model = model
+        # held weakly: the model keeps its captured step in `model._graph`, and a strong reference back would make the pair a cycle
+        # that only the cyclic collector frees -- at a moment of its choosing, which may be inside another step's stream capture.
+        # Without it the captured graphs, their pools and events go when the model goes
+        self._model = weakref.ref(model)
         self.split_side = split_side
         # a LANE of a larger batch (TrackLanes) must compute what the whole batch computes: the few-trajectory split-k rule of
         # EvalTrackModel._step_context goes by the batch it sees, so it is switched off for sub-batches
@@ -100,6 +104,10 @@ class TrackStepGraph:
             model.overlap_nets = False
             torch.cuda.synchronize(dev)
             self._capture()
+
+    @property
+    def model(self):
+        return self._model()
 
     def _capture(self):
         self.graph = torch.cuda.CUDAGraph()

@@ -328,9 +328,9 @@ class EvalTrackModel(BaseModel):
         with self._step_context(input["points"], allow_split_k):
             self._step_begin(input, npcs_input, last_pose)
             join = self._fork_rotation_net(input, npcs_input, last_pose) if self._overlap_nets(input) else None
-            if join is None and "_geom" not in npcs_input and self._l1_stream_on(npcs_input):
+            if join is None and "_cloud" not in npcs_input and self._l1_stream_on(npcs_input):
                 # networks one after the other (no fork): the shared prefix with the level-1 stream kernel all the same --
-                # CoordinateNet takes it from `_geom`, RotationNet through the shared geometry
+                # CoordinateNet takes it from `_cloud`, RotationNet from CoordinateNet's
                 self._step_prep(input, npcs_input, last_pose)
             npcs_pred = self._step_coord(npcs_input)
             if join is not None:
@@ -345,8 +345,8 @@ class EvalTrackModel(BaseModel):
         npcs_input["canon_pose"] = {k: (v if v.is_contiguous() else v.clone()) for k, v in
                                     ((k, last_pose[k][:, self.root]) for k in ("rotation", "translation", "scale"))}
         npcs_input["init_part"] = last_pose
-        for k in ("_canon", "_geom"):
-            npcs_input.pop(k, None)
+        # `_cloud` = (canonicalised cloud (B,3,N), the same (B,N,3), its geometry): the step's one hand-over of the shared prefix
+        npcs_input.pop("_cloud", None)
         input.pop("_raw", None)
 
     def _step_prep(self, input, npcs_input, last_pose, level1_only=False, side=None) -> bool:
@@ -368,8 +368,8 @@ class EvalTrackModel(BaseModel):
         geom = coord_bb.precompute_geometry(cam[1], level1_only=level1_only, side=side, stream_level1=stream_level1)
         if geom is None:
             return False
-        npcs_input["_canon"], npcs_input["_geom"] = (cam[0], cam[1]), geom
-        scratch = (geom["sa1"].get("pooled") or {}).get("_scratch")
+        npcs_input["_cloud"] = (cam[0], cam[1], geom)
+        scratch = geom.stream_scratch
         if scratch is not None:
             # STICKY give-up word: the scratch is a fresh (eager) or re-zeroed (replayed) buffer every step, so its flag says
             # something about ONE launch; this one-word OR -- a launch of the step like any other, captured and replayed with it --
@@ -406,9 +406,9 @@ class EvalTrackModel(BaseModel):
         """RotationNet up to its heads' raw per-point output (needs nothing of CoordinateNet's but, for one part, its geometry)."""
         P = self.num_parts
         last_pose = O.start_pose(last_pose)
-        cam, geom = npcs_input["_canon"], npcs_input["_geom"]
+        cam_cn, cam_n3, geom = npcs_input["_cloud"]
         if P == 1 and self.share_geometry:            # one part: RotationNet's cloud IS CoordinateNet's
-            return self.net.regress_net.raw_point_rtvec(cam[0], cam_n3=cam[1], geom=geom)
+            return self.net.regress_net.raw_point_rtvec(cam_cn, cam_n3=cam_n3, geom=geom)
         # every part's cloud canonicalised with that part's previous pose
         canon = {k: last_pose[k].reshape((-1,) + last_pose[k].shape[2:]) for k in ("rotation", "translation", "scale")}
         rcam = _canonicalize(input["points"], input["points_mean"], canon, num_parts=P)
@@ -432,9 +432,10 @@ class EvalTrackModel(BaseModel):
         input["pred_label_conf"] = npcs_pred["seg"][:, 0]
         if self.track_cfg["gt_label"] or self.track_cfg["nocs2d_label"]:
             input["pred_labels"] = npcs_input["labels"]
-        input.pop("shared_geometry", None)
-        if self.share_geometry and self.num_parts == 1 and not self.npcs_net.training:
-            input["shared_geometry"] = (self.npcs_net.last_canon, self.npcs_net.backbone.last_geom)
+        input.pop("_cloud", None)
+        cloud = npcs_pred.pop("_cloud", None)        # CoordinateNet's cloud with the geometry its backbone used
+        if self.share_geometry and self.num_parts == 1 and cloud is not None:
+            input["_cloud"] = cloud
         out = self.net(input, test_mode=True)
         pose = out["part"]
         for name in ("st_fit", "rot_pool"):
@@ -500,7 +501,7 @@ class EvalTrackModel(BaseModel):
             geom = self.npcs_net.backbone.precompute_geometry_streamed(cam[1], self.sampler_chunks, self._gstream, consumers=(side,),
                                                                        backbones=(self.net.regress_net.encoder,))
             if geom is not None:
-                npcs_input["_canon"], npcs_input["_geom"] = cam, geom
+                npcs_input["_cloud"] = (cam[0], cam[1], geom)
                 gstream = self._gstream
         if gstream is None and not self._step_prep(input, npcs_input, last_pose, level1_only=small, side=side if self.overlap_geometry else None):
             return None

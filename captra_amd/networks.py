@@ -84,9 +84,10 @@ class CoordNet(nn.Module):
         """input: {'points' (B,3,N), 'points_mean' (B,3,1), 'canon_pose' {rotation (B,3,3),
         translation (B,3,1), scale (B,)}, [...]} -> {'seg' (B,P+e,N) softmax, 'nocs' (B,3P,N), 'points'}."""
         canon_pose = input["canon_pose"]
-        # `_canon` / `_geom`: the canonicalised cloud and its geometry, when the caller already computed them
-        cam_cn, cam_n3 = input["_canon"] if "_canon" in input else _canonicalize(input["points"], input["points_mean"], canon_pose)
-        self.last_canon = (cam_cn, cam_n3)
+        # `_cloud` = (canonicalised cloud (B,3,N), the same (B,N,3), its geometry or None): ONE private key for this hand-over.  In the
+        # input when the caller already computed it (EvalTrackModel's shared prefix); in the prediction, with the geometry the
+        # backbone used, for whoever runs a second network on the same cloud (popped before the dict leaves the step)
+        cam_cn, cam_n3, geom = input["_cloud"] if "_cloud" in input else (*_canonicalize(input["points"], input["points_mean"], canon_pose), None)
         fused_tail = None
         if (not self.training) and cam_cn.is_cuda:
             head_layers = self._head_layers(cam_cn.device)
@@ -107,7 +108,7 @@ class CoordNet(nn.Module):
                                                                       act=fused.ACT_SIGMOID_M05)
                     seg_logits, nocs = self._heads(fused.mlp_chain3(x, layers, fused.ACT_RELU))
                     return seg_logits, nocs - 0.5
-        out = self.backbone(cam_cn, input_n3=cam_n3, geom=input.get("_geom"), finish=fused_tail)
+        out = self.backbone(cam_cn, input_n3=cam_n3, geom=geom, finish=fused_tail)
         if fused_tail is not None:
             seg_logits, nocs_m05 = out
         else:
@@ -125,6 +126,8 @@ class CoordNet(nn.Module):
             pred = {"seg": seg, "nocs": nocs_m05, "points": cam_cn, "_labels_i32": self.last_labels_i32}
         else:
             pred = {"seg": F.softmax(seg_logits, dim=1), "nocs": nocs_m05, "points": cam_cn}
+        if not self.training:
+            pred["_cloud"] = (cam_cn, cam_n3, self.backbone.last_geom)
         if "gt_part" in input:
             pred["part"] = self._fit_with_gt_rotation(input, pred, test)
         return pred
@@ -263,15 +266,15 @@ class PartCanonNet(nn.Module):
         B = len(input["points"])
 
         # every part sees the whole cloud, canonicalised with that part's previous pose
-        # `shared` = (canonicalised cloud, backbone geometry) of CoordNet, valid when this net's clouds are
-        # the same clouds (one part: the part's previous pose IS the CoordNet's canonical pose)
-        shared = input.get("shared_geometry") if P == 1 else None
+        # `shared` = CoordNet's `_cloud` (canonicalised cloud in both layouts, backbone geometry), valid when this net's clouds
+        # are the same clouds (one part: the part's previous pose IS the CoordNet's canonical pose)
+        shared = input.get("_cloud") if P == 1 else None
         fast = (eval_rnpcs and test_mode and not self.return_point_rotation and not self.training and input["points"].is_cuda
                 and fused.USE_ROT_READOUT)
         if fast and input.get("_raw") is not None:
             cam_cn, cam_n3, geom = input["points"], None, None      # the heads already ran (side stream): nothing to canonicalise
         elif shared is not None:
-            (cam_cn, cam_n3), geom = shared
+            cam_cn, cam_n3, geom = shared
         else:
             cam_cn, cam_n3 = _canonicalize(input["points"], input["points_mean"], canon_pose, num_parts=P)
             geom = None

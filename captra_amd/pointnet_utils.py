@@ -27,6 +27,7 @@ import torch.nn.functional as F
 
 from . import fused
 from .fold import fold_conv_bn
+from .geometry import LevelGeometry
 from .pointnet_lib import pointnet2_utils as futils
 
 
@@ -175,29 +176,27 @@ class PointNetSetAbstractionMsg(_FoldCache, nn.Module):
 
     def forward(self, xyz, points, xyz_n3=None, geom=None):
         """xyz (B,3,N), points (B,D,N) or None -> (new_xyz (B,3,S), features (B,D',S)).
-        `xyz_n3` optionally passes the (B,N,3) copy the caller already has; `geom` the sampling and
+        `xyz_n3` optionally passes the (B,N,3) copy the caller already has; `geom` a `LevelGeometry`: the sampling and
         neighbour lists another network computed on the SAME cloud (FPS and ball query depend on the
-        coordinates only).  The geometry used is left in `self.last_geom`."""
+        coordinates only) -- what it lacks is computed here and left in it."""
         if not _has_points(points):
             points = None
         if xyz_n3 is None:
             xyz_n3 = xyz.transpose(1, 2).contiguous()
         if geom is None:
+            geom = LevelGeometry()
+        if geom.new_xyz_n3 is None:
             sampled = fused.fps_gather(xyz_n3.contiguous(), self.npoint) if self._can_fuse(xyz) else None
             if sampled is not None:                                                          # one launch
-                _, new_xyz_n3, new_xyz_cn = sampled
-                geom = {"new_xyz_n3": new_xyz_n3, "new_xyz": new_xyz_cn, "idx_list": None}
+                _, geom.new_xyz_n3, geom.new_xyz = sampled
             else:
                 fps_idx = futils.furthest_point_sample(xyz_n3, self.npoint)                  # (B,S) int32
-                new_xyz_n3 = torch.gather(xyz_n3, 1, fps_idx.long().unsqueeze(-1).expand(-1, -1, 3))  # (B,S,3)
-                geom = {"new_xyz_n3": new_xyz_n3, "new_xyz": new_xyz_n3.transpose(1, 2).contiguous(), "idx_list": None}
-        new_xyz_n3, new_xyz = geom["new_xyz_n3"], geom["new_xyz"]
-        self.last_new_xyz_n3 = new_xyz_n3
-        self.last_geom = geom
-        pooled = geom.get("pooled")
-        if pooled is not None and id(self) in pooled:
+                geom.new_xyz_n3 = torch.gather(xyz_n3, 1, fps_idx.long().unsqueeze(-1).expand(-1, -1, 3))  # (B,S,3)
+                geom.new_xyz = geom.new_xyz_n3.transpose(1, 2).contiguous()
+        new_xyz_n3, new_xyz = geom.new_xyz_n3, geom.new_xyz
+        if self in geom.pooled:
             # the level-1 stream kernel (fused.sa1_stream_bf16) ran this level beside the sampler: nothing left to launch
-            return new_xyz, pooled[id(self)]
+            return new_xyz, geom.pooled[self]
         if self._can_fuse(xyz):
             return new_xyz, self._forward_fused(xyz.contiguous(), xyz_n3, points, new_xyz_n3, geom)
         return new_xyz, self._forward_layers(xyz, xyz_n3, points, new_xyz, new_xyz_n3)
@@ -206,17 +205,17 @@ class PointNetSetAbstractionMsg(_FoldCache, nn.Module):
     def _forward_fused(self, xyz_cn, xyz_n3, points, new_xyz_n3, geom):
         folded = self._fold(xyz_cn.device)
         B, S = xyz_cn.shape[0], self.npoint
-        if geom["idx_list"] is None:
-            geom["idx_list"] = fused.ball_query_multi(self.radius_list, self.nsample_list, xyz_n3, new_xyz_n3)
-        idx_list = geom["idx_list"]
+        if geom.idx_list is None:
+            geom.idx_list = fused.ball_query_multi(self.radius_list, self.nsample_list, xyz_n3, new_xyz_n3)
+        idx_list = geom.idx_list
         out = torch.empty(B, self.out_channel, S, dtype=torch.float32, device=xyz_cn.device)
         feat = points.contiguous() if points is not None else None
-        if geom.get("chunks"):
+        if geom.windows:
             # STREAMED sampling (backbones.precompute_geometry_streamed): the sampler is still picking the later centres on its
             # own stream; every window of centres runs its scales as soon as its picks and neighbour lists are there
             cur = torch.cuda.current_stream(xyz_cn.device)
             cfeat = 0 if feat is None else feat.shape[1]
-            for m0, mc, ev in geom["chunks"]:
+            for m0, mc, ev in geom.windows:
                 cur.wait_event(ev)
                 off = 0
                 with fused.centre_window(m0, mc):
@@ -324,12 +323,11 @@ class PointNetFeaturePropagation(_FoldCache, nn.Module):
     def forward(self, xyz1, xyz2, points1, points2, xyz1_n3=None, xyz2_n3=None, nn=None, tail=None, finish=None):
         """xyz1 (B,3,N) dense, xyz2 (B,3,S) sparse, points1 (B,D1,N) or None, points2 (B,D2,S)
         -> (B,D',N).  `nn` = (idx, weight) of fused.three_nn_weights on the same coordinates, when
-        another network already computed them; what was used is left in `self.last_nn`.
+        another network already computed them (None: computed here).
         `tail` (fused path only) = a folded conv+BN+ReLU layer the caller applies to the result anyway
         (the backbone's conv1): it is appended to this module's MLP so that the chain runs as one launch.
         `finish(new_points, layers)` (fused path only), when given, replaces the evaluation of those layers: the caller
         runs them together with whatever consumes their output (CoordNet's heads) and gets back what it returns."""
-        self.last_nn = None
         B, _, N = xyz1.shape
         S = xyz2.shape[2]
         if not _has_points(points1):
@@ -381,7 +379,6 @@ class PointNetFeaturePropagation(_FoldCache, nn.Module):
             if fuse:
                 if nn is None:
                     nn = fused.three_nn_weights(xyz1_n3, xyz2_n3)
-                self.last_nn = nn
                 if (points1 is not None and tail is None and finish is None and fused.mlp_dtype() == "bf16"
                         and fused.neck_chain_supported(points1.shape[1] + points2.shape[1], N, self._fold(xyz1.device), points1.shape[1], 2)):
                     # interpolation, skip concat and both layers in one launch (csrc/neck_bf16.hip): the interpolated channels are

@@ -116,7 +116,8 @@ class CanonCoordModel(BaseModel):
         self.loss_dict = {}
         with torch.no_grad():
             self.pred_dict = self.net(self.feed_dict, test=True)
-            self.pred_dict.pop("_labels_i32", None)      # (the track loop's private hand-over: not part of the reference's dict)
+            for key in ("_labels_i32", "_cloud"):        # (the track loop's private hand-overs: not part of the reference's dict)
+                self.pred_dict.pop(key, None)
             if not no_eval:
                 self.compute_loss(test=True)
 
