@@ -110,6 +110,7 @@ _SIGNATURES = {
     "captra_part_fit_ransac_sym": [_INT, _INT, _INT, _INT, _F, _P, _P, _P, _INT, _P, _P, C.c_ulonglong] + [_P] * 8,
     "captra_part_fit_guard_sym": [_INT, _INT, _INT, _INT] + [_P] * 7 + [_F, _INT, _INT, _INT, _INT, _INT, C.c_ulonglong] + [_P] * 8,
     "captra_part_fit_st_ransac": [_INT] * 6 + [_F, _P, _P, _P, _INT] + [_P] * 5 + [C.c_ulonglong] + [_P] * 6,
+    "captra_part_fit_st_size": [_INT] * 6 + [_F, _P, _P, _P, _INT] + [_P] * 5 + [C.c_ulonglong] + [_P] * 6 + [_INT, _F, _INT, _INT] + [_P] * 16,
     "captra_rot_pool_consensus": [_INT] * 7 + [_F] + [_P] * 4 + [C.c_ulonglong] + [_P] * 6,
     "captra_pose_extrapolate": [_INT, _INT, _INT] + [_P] * 6 + [_F, _F, _F] + [_P] * 7,
     "captra_seg_softmax_argmax": [_INT, _INT, _INT, _P, _P, _P, _P],

@@ -180,6 +180,21 @@ struct RsGivenRot {
     }
 };
 
+// RsGivenRotScale: the rotation R0 AND the scale s are given, the translation is fitted -- captra_part_fit_st with given_scale on a
+// set of pairs: RsGivenRot with s in place of ps_scale (SYM still takes the in-plane rotation from the moments first: that step does
+// not depend on s).  The solver of captra_part_fit_st_size's held fit (pose_size.hip).
+template <bool SYM>
+struct RsGivenRotScale {
+    double R0[9], s;
+    __device__ void operator()(const double M[9], const double C6[6], const double sb[3], const double tb[3], double R[9], double *sc_out,
+                               double tr[3]) const {
+        if constexpr (SYM) ps_rot_about_y(R0, M, R);
+        else for (int i = 0; i < 9; ++i) R[i] = R0[i];
+        *sc_out = s;
+        ps_trans(R, s, sb, tb, tr);
+    }
+};
+
 // What rs_fit found: best / ninl are uniform over the workgroup, ok and the pose are thread 0's (identity / 1 / 0 when not ok).
 struct RsResult {
     int best = 0, ninl = 0;

@@ -145,6 +145,34 @@ def motion_table(name: str, data: dict) -> list:
     return lines
 
 
+def size_table(name: str, data: dict) -> list:
+    """The held size's record of one result pickle (present when the run had track_cfg/size/hold): one line per part with the frames
+    whose scale was held at the running mean, the frames accepted into the mean, the frames kept out of it (gated by max_ratio, or
+    without a valid fit of their own) and the restarts (an accepted frame that left ONE frame in a mean that had some), the final
+    mean -- replayed in float64 from the record, starting at frame 0's scale -- and the smallest and largest free scale, over the
+    frames whose own fit was valid where the pickle also carries the robust fit's record, else over all frames."""
+    frames = [(i, {k: np.asarray(r[k]).reshape(-1) for k in ("held", "accepted", "free", "n")}) for i, r in enumerate(data["size"])
+              if r is not None and "held" in r]
+    st = data.get("st_fit")
+    lines = []
+    for p in range(len(frames[0][1]["held"]) if frames else 0):
+        mean, prev_n, restarts, free = float(np.asarray(data["pred"]["poses"][0]["scale"]).reshape(-1)[p]), None, 0, []
+        for i, r in frames:
+            n, f = int(r["n"][p]), float(r["free"][p])
+            if int(r["accepted"][p]) != 0:
+                restarts += int(n == 1 and prev_n is not None and prev_n >= 1)
+                mean = f if n == 1 else mean + (f - mean) / n
+            prev_n = n
+            if st is None or st[i] is None or int(np.asarray(st[i]["valid"]).reshape(-1)[p]) != 0:
+                free.append(f)
+        held = sum(1 for _, r in frames if int(r["held"][p]) != 0)
+        accepted = sum(1 for _, r in frames if int(r["accepted"][p]) != 0)
+        span = f"free scale min {min(free):.5f} max {max(free):.5f}" if free else "free scale -"
+        lines.append(f"{name} part {p}: held {held}; accepted {accepted}; gated or invalid {len(frames) - accepted}; restarted {restarts} "
+                     f"(of {len(frames)} frames); final mean {mean:.5f} over {prev_n if prev_n is not None else 0} frames; {span}")
+    return lines
+
+
 def otf_thin_table(name: str, data: dict) -> list:
     """The re-crop's on-device thinning record of one result pickle (present when the run had track_cfg/otf_thin/device): one line
     with the frames whose candidate list was thinned, of the frames re-cropped."""
@@ -175,6 +203,7 @@ RECORD_TABLES = (
     ("st_fit", st_fit_table, "robust scale / translation fit (track_cfg/st_fit), frames per trajectory and part:"),
     ("rot_pool", rot_pool_table, "consensus rotation read-out (track_cfg/rot_pool), per trajectory and part:"),
     ("motion", motion_table, "constant-velocity start pose (track_cfg/motion), per trajectory and part:"),
+    ("size", size_table, "held size (track_cfg/size), frames per trajectory and part:"),
     ("otf_thin", otf_thin_table, "re-crop lists thinned on the device (track_cfg/otf_thin), frames per trajectory:"),
     ("depth_filter", depth_filter_table, "flying depth pixels removed at upload (track_cfg/depth_filter), per trajectory:"),
     ("image_fit", image_fit_table, "first pose fitted from frame 0's images (init_frame/image_fit), per trajectory:"),

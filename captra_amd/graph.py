@@ -10,6 +10,7 @@ The reference has no equivalent (eager PyTorch, one ATen launch at a time, model
 from __future__ import annotations
 
 import os
+import types
 import weakref
 
 import torch
@@ -70,9 +71,8 @@ class TrackStepGraph:
         # a LANE of a larger batch (TrackLanes) must compute what the whole batch computes: the few-trajectory split-k rule of
         # EvalTrackModel._step_context goes by the batch it sees, so it is switched off for sub-batches
         self.allow_split_k = allow_split_k
-        if getattr(model, "motion", None) is not None:
-            from .track_options import entering_pose
-            pose = entering_pose(pose)          # track_cfg/motion: the captured buffers hold the travelling dict, prediction included
+        from .track_options import entering
+        pose = entering(pose, model)            # track_cfg/motion, track_cfg/size: the captured buffers hold the travelling dict, prediction and size state included
         self.b0 = int(b0)          # a lane's first trajectory within the whole batch: the track guard draws by it (a launch argument, captured)
         dev = points.device
         self.points = points.clone()
@@ -193,13 +193,16 @@ class TrackStepGraph:
         pairs = [(points, self.points), (points_mean, self.points_mean)]
         if pose is not self.pose:          # (a lane of TrackLanes hands its pose over in place)
             if len(pose) < len(self.pose):
-                from .track_options import entering_pose
-                pose = entering_pose(pose)      # track_cfg/motion: a dict without a prediction is a track's start
+                from .track_options import entering
+                pose = entering(pose, self.model)   # track_cfg/motion, track_cfg/size: a dict without prediction / size state is a track's start
             pairs += [(pose[k], self.pose[k]) for k in self.pose]
         if self.labels is not None and labels is not None:
             pairs.append((labels, self.labels))
         # the step's inputs into the captured buffers: one launch when they are plain device tensors of the captured types
         if all(a.is_cuda and a.is_contiguous() and a.dtype == b.dtype and a.shape == b.shape and a.element_size() % 4 == 0 for a, b in pairs):
+            # (points, mean, the pose dict -- 3 keys, 6 with the motion model, 9 with the size state too -- and labels: at most 12 jobs,
+            # within the launch's 16)
+            assert len(pairs) <= 16, len(pairs)
             fused.copy_multi(pairs)
         else:
             for a, b in pairs:
@@ -231,7 +234,8 @@ class TrackLanes:
         B = points.shape[0]
         if lanes < 1 or B % lanes:
             raise ValueError(f"{B} trajectories do not split into {lanes} lanes")
-        self.motion = getattr(model, "motion", None) is not None
+        # (the options whose state travels in the pose dict: what track_options.entering reads of a model)
+        self._options = types.SimpleNamespace(motion=getattr(model, "motion", None), size=getattr(model, "size", None))
         pose = self._entering(pose)
         dev = points.device
         per = B // lanes
@@ -255,11 +259,9 @@ class TrackLanes:
         return any(g.stale() for g in self.graphs)
 
     def _entering(self, pose: dict) -> dict:
-        """track_cfg/motion: the travelling dict (track_options.entering_pose); else `pose` itself."""
-        if not self.motion:
-            return pose
-        from .track_options import entering_pose
-        return entering_pose(pose)
+        """track_cfg/motion, track_cfg/size: the travelling dict (track_options.entering); else `pose` itself."""
+        from .track_options import entering
+        return entering(pose, self._options)
 
     def set_pose(self, pose: dict) -> None:
         """(Re)start the trajectories from `pose` (B-major dict) — the initial pose of the track loop (model.py:394)."""
@@ -291,7 +293,8 @@ class TrackLanes:
                 if self.npcs_ring is not None:
                     pairs += [(g.npcs_pred[k], dst[s]) for k, dst in self.npcs_ring[slot].items()]
                 # (6 pose + 3 map jobs, 4 more with a guard record, 2 with the robust fit's: 15, within the launch's 16; the consensus
-                # read-out's 2 on top of all of them take a second launch, and so do the motion model's 6 pose + 5 record jobs)
+                # read-out's 2 on top of all of them take a second launch, and so do the motion model's 6 pose + 5 record jobs and the
+                # size state's 6 pose + 4 record jobs)
                 for j in range(0, len(pairs), 16):
                     fused.copy_multi(pairs[j:j + 16])
                 self.written[slot][l].record(st)

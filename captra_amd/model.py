@@ -129,6 +129,7 @@ class EvalTrackModel(BaseModel):
         self.st_fit = self.net.st_fit = O.st_fit_cfg(cfg)                  # every step's scale / translation by RANSAC
         self.rot_pool = self.net.rot_pool = O.rot_pool_cfg(cfg)            # every step's rotation from the votes' consensus
         self.motion = O.motion_cfg(cfg)                                    # every step starts from a constant-velocity prediction
+        self.size = self.net.size = O.size_cfg(cfg)                        # every step holds the part's running scale
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
         self.otf_thin = O.otf_thin_cfg(cfg)                                # the re-crop's over-long lists thinned on the device
         self._otf_thin_rec = {}             # frame -> {first trajectory of a slice: its thinned flags (b,) int32 on the device}
@@ -323,8 +324,7 @@ class EvalTrackModel(BaseModel):
         of the first trajectory within the whole batch when `input` is a lane of one (the guard's draws; default 0).
         track_cfg/motion: `last_pose` carries the prediction the step starts from (a dict without one is a track's start) and the
         returned dict the next one; the four phases take the dict as it travels and read their start pose out of it."""
-        if self.motion is not None:
-            last_pose = O.entering_pose(last_pose)
+        last_pose = O.entering(last_pose, self)      # (track_cfg/size: likewise the size state; a dict without one is a track's start)
         with self._step_context(input["points"], allow_split_k):
             self._step_begin(input, npcs_input, last_pose)
             join = self._fork_rotation_net(input, npcs_input, last_pose) if self._overlap_nets(input) else None
@@ -438,13 +438,18 @@ class EvalTrackModel(BaseModel):
             input["_cloud"] = cloud
         out = self.net(input, test_mode=True)
         pose = out["part"]
-        for name in ("st_fit", "rot_pool"):
+        for name in ("st_fit", "rot_pool", "size"):
             if getattr(self, name) is not None:
-                # the option's record joins CoordinateNet's maps (`st_*`, `rot_*`), so it travels with them through every batch form
+                # the option's record joins CoordinateNet's maps (`st_*`, `rot_*`, `size_*`), so it travels with them through every batch form
                 O.put_record(npcs_pred, name, out[name])
+        # track_cfg/size: the fit returned the new size state beside the (held) pose; the guard judges that pose and its re-fit
+        # replaces it, scale included, without touching the state; the motion model never touches the scale
+        size_state = {k: pose[k] for k in O.SIZE_KEYS} if self.size is not None else None
         if self.guard is not None:
             pose = self._guard_step(input, npcs_pred, pose)
-        return pose if self.motion is None else self._motion_step(npcs_pred, entered, pose)
+        if self.motion is not None:
+            pose = self._motion_step(npcs_pred, entered, pose)
+        return pose if size_state is None else {**{k: v for k, v in pose.items() if k not in size_state}, **size_state}
 
     def _motion_step(self, npcs_pred, entered, pose):
         """The motion model behind the fit and the guard: the pose the NEXT step starts from, out of the result that entered this
@@ -786,7 +791,8 @@ class EvalTrackModel(BaseModel):
                 frames = self._batch_frames
             with torch.no_grad():
                 # (track_cfg/motion: the travelling dict carries the prediction beside the pose; frame 0's is a track's start)
-                run_frame, commit, poses, bounds, join = frames(pred_poses[0] if self.motion is None else O.entering_pose(pred_poses[0]))
+                # (track_cfg/size: likewise the size state)
+                run_frame, commit, poses, bounds, join = frames(O.entering(pred_poses[0], self))
                 commit = O.commit_with_records(commit, records)
                 pending = None                  # (frame, poses that entered it, its deferred checks)
 

@@ -17,7 +17,7 @@ from .backbones import PointNet2Msg
 from .blocks import RotationRegressor, get_point_mlp, run_point_mlp
 from .fold import fold_conv_bn
 from .pose_utils.part_dof_utils import convert_pred_rtvec_to_matrix, merge_reenact_canon_part_pose
-from .pose_utils.pose_fit import part_fit_st_cn, part_fit_st_ransac_track, part_fit_st_track
+from .pose_utils.pose_fit import SIZE_STATE_KEYS, part_fit_st_cn, part_fit_st_ransac_track, part_fit_st_size_track, part_fit_st_track
 from .pose_utils.procrustes import (rot_around_yaxis_to_3d, scale_pts_mask, transform_pts_2d_mask,
                                     translate_pts_mask)
 
@@ -229,6 +229,30 @@ class PartCanonNet(nn.Module):
         # ever; {'angle_th' (degrees), 'num_hyps', 'seed'} (EvalTrackModel sets it from track_cfg/rot_pool) = the mean of the votes within
         # angle_th of the best-supported one
         self.rot_pool = None
+        # HOLDING the part's running scale in the tracking step (captra_part_fit_st_size): None = every frame's own scale, as ever;
+        # {'max_ratio', 'min_frames', 'max_frames', 'reset_after', ...} (EvalTrackModel sets it from track_cfg/size): the state comes
+        # in with input['state']['part'] (size_mean / size_n / size_miss) and leaves beside the pose's three keys
+        self.size = None
+
+    def _size_fit(self, input, labels_i32, npcs, rotation, part_pose):
+        """test_mode with `size` set: the step's fit, then the size state's decision and, where the size is held, the translation with
+        the scale given -- robust mode (`st_fit` set) in the robust fit's place, one launch; plain mode one launch behind the one-pass
+        fit.  -> {'part': the pose with the new state beside it, 'size': the frame's record[, 'st_fit': the FREE robust fit's]}."""
+        z, st = self.size, self.st_fit
+        points = input["points"].float().contiguous()
+        state = {k: part_pose[k] for k in SIZE_STATE_KEYS}
+        opts = {k: z[k] for k in ("min_frames", "max_ratio", "max_frames", "reset_after")}
+        args = (labels_i32, npcs, points, input["points_mean"], rotation, part_pose["scale"], part_pose["translation"], self.sym, state)
+        if st is not None:
+            pose, new, info = part_fit_st_size_track(*args, **opts, inlier_th=st["inlier_th"], num_hyps=st["num_hyps"], seed=st["seed"],
+                                                     b0=int(input.get("b0", 0)))
+        else:
+            pose, new, info = part_fit_st_size_track(*args, **opts, free=part_fit_st_track(*args[:8]))
+        out = {"part": {"rotation": rotation, "scale": pose["scale"], "translation": pose["translation"], **new},
+               "size": {k: info[k] for k in ("held", "accepted", "free", "n")}}
+        if st is not None:
+            out["st_fit"] = {"inliers": info["inliers"], "valid": info["free_valid"]}
+        return out
 
     def _robust_rotation(self, input, raw, labels_i32, part_pose):
         """test_mode with `rot_pool` set: the step's rotation from the heads' raw output (B*P,R,N) by the consensus read-out.
@@ -292,6 +316,8 @@ class PartCanonNet(nn.Module):
             else:
                 rotation = fused.rot_pool_compose(raw, labels_i32, part_pose["rotation"].float().contiguous(), self.sym)
             npcs = input["pred_nocs"].reshape(B, P, 3, -1).float().contiguous()
+            if self.size is not None:
+                return {**self._size_fit(input, labels_i32, npcs, rotation, part_pose), **extra}
             if self.st_fit is not None:
                 pose, record = self._robust_fit(input, labels_i32, npcs, rotation, part_pose)
                 return {"part": pose, "st_fit": record, **extra}
@@ -332,6 +358,12 @@ class PartCanonNet(nn.Module):
             labels = input["pred_labels"] if test_mode else input["labels"]
             fit_rot = rotation if test_mode else input["gt_part"]["rotation"]
             npcs = input["pred_nocs"].reshape(B, P, 3, -1).float().contiguous()
+            if test_mode and self.size is not None:
+                # (layer by layer: the same launches as the fast path -- the one-pass fit's track form in plain mode)
+                ret = {**self._size_fit(input, labels.int().contiguous(), npcs, rotation.float().contiguous(), part_pose), **extra}
+                if "point_rotation" in out:
+                    ret["point_rotation"] = out["point_rotation"]
+                return ret
             if test_mode and self.st_fit is not None:
                 # (no `where` below: the kernel keeps the previous values of an invalid fit)
                 final_pose, record = self._robust_fit(input, labels.int().contiguous(), npcs, rotation.float().contiguous(), part_pose)

@@ -50,6 +50,11 @@ _FLAGS = [  # (name, type, default)
     # (degrees) and max_shift (a fraction of data_radius) are required
     ("track_cfg/motion/predict", boolean_string, None), ("track_cfg/motion/max_angle", float, None),
     ("track_cfg/motion/max_shift", float, None), ("track_cfg/motion/gain", float, None),
+    # every step holds the part's running scale (track_options.py: size_cfg); off unless hold is True, and then max_ratio is required.
+    # Not given = not in the namespace at all, like yaxis_only
+    ("track_cfg/size/hold", boolean_string, argparse.SUPPRESS), ("track_cfg/size/max_ratio", float, argparse.SUPPRESS),
+    ("track_cfg/size/min_frames", int, argparse.SUPPRESS), ("track_cfg/size/max_frames", int, argparse.SUPPRESS),
+    ("track_cfg/size/reset_after", int, argparse.SUPPRESS), ("track_cfg/size/init_frames", int, argparse.SUPPRESS),
     # optimisation
     ("total_epoch", int, None), ("optimizer", str, None), ("weight_decay", float, None), ("learning_rate", float, None),
     ("lr_policy", str, None), ("lr_gamma", float, None), ("lr_step_size", int, None), ("lr_clip", float, None), ("freq/save", int, None),

@@ -167,6 +167,55 @@ def part_fit_st_ransac(labels, source, target, rotation, cfg, inlier_th=1e-3, nu
     return model, filter_model_valid(model, valid.bool())
 
 
+SIZE_STATE_KEYS = ("size_mean", "size_n", "size_miss")      # the size state as it travels in the pose dict
+
+
+def part_fit_st_size_track(labels_i32, src_cn, pts_cn, pts_mean, rotation, prev_scale, prev_trans, sym: bool, state, min_frames, max_ratio,
+                           max_frames=None, reset_after=None, free=None, inlier_th=0.0, num_hyps=64, seed=0, b0=0, sample_rank=None):
+    """Holding the track's size in one launch (captra_part_fit_st_size, include/captra_hip.h): part_fit_st_track's arguments, the size
+    state {'size_mean' (B,P) float32, 'size_n', 'size_miss' (B,P) int32} and its options.  free = (scale (B,P), translation (B,P,3[,1]),
+    valid (B,P)) of part_fit_st_track on the same arguments: PLAIN mode (inlier_th, num_hyps, seed, b0, sample_rank are not used);
+    free = None: ROBUST mode, the kernel computes part_fit_st_ransac_track's fit itself (in place of that launch) from its arguments.
+    -> ({'scale' (B,P), 'translation' (B,P,3,1), 'valid' (B,P) bool}, the new state, info {'held', 'accepted', 'n' (B,P) int32,
+        'free' (B,P) float32: the record; 'free_translation' (B,P,3,1), 'free_valid' (B,P) int32, 'held_inliers', 'held_best' (B,P) int32
+        [, 'inliers', 'best' (B,P) int32: the free robust fit's]})."""
+    B, P, _, N = src_cn.shape
+    dev = src_cn.device
+    pts_mean = pts_mean.reshape(B, 3).float().contiguous()
+    prev_scale = prev_scale.float().contiguous()
+    prev_trans = prev_trans.reshape(B, P, 3).float().contiguous()
+    mean_in, n_in, miss_in = (state[k].contiguous() for k in SIZE_STATE_KEYS)
+    assert mean_in.dtype == torch.float32 and n_in.dtype == torch.int32 and miss_in.dtype == torch.int32 and mean_in.shape == (B, P)
+    robust = free is None
+    if robust:
+        if sample_rank is not None:
+            sample_rank = sample_rank.reshape(B, P, int(num_hyps), 3).int().contiguous()
+        free_in = (None, None, None)
+    else:
+        num_hyps, sample_rank = 0, None
+        free_in = (free[0].float().contiguous(), free[1].reshape(B, P, 3).float().contiguous(), free[2].int().contiguous())
+    L.require_device(labels_i32, src_cn, pts_cn, pts_mean, rotation, prev_scale, prev_trans, sample_rank, mean_in, n_in, miss_in, *free_in)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    i32 = lambda: torch.empty(B, P, dtype=torch.int32, device=dev)
+    scale, trans, valid = f32(B, P), f32(B, P, 3), i32()
+    free_out = (f32(B, P), f32(B, P, 3), i32(), i32(), i32()) if robust else (None,) * 5
+    mean_out, n_out, miss_out, held, accepted, held_best, held_inl = f32(B, P), i32(), i32(), i32(), i32(), i32(), i32()
+    with torch.cuda.device(dev):
+        L.call("captra_part_fit_st_size", B, P, N, 1 if sym else 0, int(b0), int(num_hyps), float(inlier_th), L.ptr(labels_i32), L.ptr(src_cn),
+               L.ptr(pts_cn), 0, L.ptr(pts_mean), L.ptr(rotation), L.ptr(prev_scale), L.ptr(prev_trans), L.ptr(sample_rank),
+               int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(free_in[0]), L.ptr(free_in[1]), L.ptr(free_in[2]), L.ptr(mean_in), L.ptr(n_in),
+               L.ptr(miss_in), int(min_frames), float(max_ratio), int(max_frames or 0), int(reset_after or 0), L.ptr(scale), L.ptr(trans),
+               L.ptr(valid), *(L.ptr(t) for t in free_out), L.ptr(mean_out), L.ptr(n_out), L.ptr(miss_out), L.ptr(held), L.ptr(accepted),
+               L.ptr(held_best), L.ptr(held_inl))
+    fs, ft, fv = free_out[:3] if robust else free_in
+    info = {"held": held, "accepted": accepted, "free": fs, "n": n_out, "free_translation": ft.unsqueeze(-1), "free_valid": fv,
+            "held_inliers": held_inl, "held_best": held_best}
+    if robust:
+        info["inliers"], info["best"] = free_out[4], free_out[3]
+    return ({"scale": scale, "translation": trans.unsqueeze(-1), "valid": valid.bool()},
+            {"size_mean": mean_out, "size_n": n_out, "size_miss": miss_out}, info)
+
+
 GUARD_VERDICTS = ("ok", "too_few", "lost", "recovered")      # the codes 0..3 of captra_part_fit_guard
 
 

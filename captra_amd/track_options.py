@@ -183,9 +183,57 @@ def motion_cfg(cfg):
     return vals
 
 
-# The pose dict that travels from frame to frame: these three, and with track_cfg/motion three more -- the pose the next step starts
-# from and whether the dict's own pose is a measured result (a track's start is not).  The dict is the loop's whole state.
+def size_cfg(cfg):
+    """track_cfg: {size: {hold: True, max_ratio: <ratio>, min_frames: 1, max_frames: None, reset_after: None, init_frames: 0}}: every
+    step keeps the running mean of each part's scale -- a rigid part's NOCS scale is a constant of the instance -- and, once min_frames
+    frames are in it, HOLDS the pose's scale at that mean and fits the translation with the scale given (csrc/pose_size.hip,
+    include/captra_hip.h: captra_part_fit_st_size -- in place of the robust fit's launch, or one launch behind the one-pass fit's,
+    captured with the step).  A frame whose own (free) scale is more than max_ratio away from an established mean is gated out of the
+    mean; reset_after such frames in a row restart it; max_frames caps the averaging window.  The state travels in the pose dict
+    (size_mean, size_n, size_miss) and is recorded per frame (pred_dict / pickle 'size').  None when absent or hold is not set;
+    max_ratio has no default -- it depends on the trained network's scale scatter --; init_frames: how many frames the track's first
+    pose counts for (>= min_frames: its size is held from frame 1 on and then averaged in)."""
+    s = cfg["track_cfg"].get("size")
+    if s is None or not s.get("hold", False):
+        return None
+    ratio = s.get("max_ratio")
+    if ratio is None:
+        raise ValueError("track_cfg/size/hold needs track_cfg/size/max_ratio (the largest ratio between a frame's scale and the running "
+                         "mean, > 1): it has no default")
+    ratio = float(np.float32(ratio))        # (the kernel's argument is fp32)
+    if not (ratio > 1.0 and np.isfinite(ratio)):
+        raise ValueError(f"track_cfg/size/max_ratio must be a finite ratio > 1, got {s.get('max_ratio')!r}")
+    out = {"max_ratio": ratio}
+    for key, default, lo in (("min_frames", 1, 1), ("max_frames", None, 1), ("reset_after", None, 1), ("init_frames", 0, 0)):
+        v = s.get(key)
+        v = default if v is None else v
+        if v is not None:
+            if isinstance(v, bool) or int(v) != v or not lo <= int(v) < 2 ** 31:
+                raise ValueError(f"track_cfg/size/{key} must be an integer >= {lo}, got {s.get(key)!r}")
+            v = int(v)
+        out[key] = v
+    return out
+
+
+# The pose dict that travels from frame to frame: these three, with track_cfg/motion three more -- the pose the next step starts
+# from and whether the dict's own pose is a measured result (a track's start is not) -- and with track_cfg/size the three words of
+# the size state.  The dict is the loop's whole state.
 POSE_KEYS = ("rotation", "scale", "translation")
+SIZE_KEYS = ("size_mean", "size_n", "size_miss")
+
+
+def entering_size(pose, size):
+    """track_cfg/size: a dict without the size state is a track's START -- the state is the start pose's scale counted as init_frames
+    frames where it is finite and > 0, else empty (n = 0, mean = 0).  A dict that carries its state passes through."""
+    if "size_mean" in pose:
+        return pose
+    import torch
+    scale = pose["scale"].float()
+    ok = torch.isfinite(scale) & (scale > 0)
+    if size["init_frames"] == 0:
+        ok = torch.zeros_like(ok)
+    n = torch.where(ok, torch.full_like(scale, size["init_frames"], dtype=torch.int32), torch.zeros_like(scale, dtype=torch.int32))
+    return {**pose, "size_mean": torch.where(ok, scale, torch.zeros_like(scale)), "size_n": n, "size_miss": torch.zeros_like(n)}
 
 
 def entering_pose(pose):
@@ -198,11 +246,22 @@ def entering_pose(pose):
             "measured": torch.zeros(pose["scale"].shape, dtype=torch.int32, device=pose["scale"].device)}
 
 
+def entering(pose, model):
+    """The travelling dict of `model`'s options (its `motion` / `size` attributes; absent or None: off) for a pose entering a step."""
+    if getattr(model, "motion", None) is not None:
+        pose = entering_pose(pose)
+    if getattr(model, "size", None) is not None:
+        pose = entering_size(pose, model.size)
+    return pose
+
+
 def start_pose(pose):
     """The pose a step starts from: the prediction where the dict carries one (scale has no velocity), else the dict itself."""
     if "next_rotation" not in pose:
         return pose
-    return {"rotation": pose["next_rotation"], "scale": pose["scale"], "translation": pose["next_translation"]}
+    start = {"rotation": pose["next_rotation"], "scale": pose["scale"], "translation": pose["next_translation"]}
+    start.update((k, pose[k]) for k in SIZE_KEYS if k in pose)      # (track_cfg/size: the state stays with the pose it belongs to)
+    return start
 
 
 # ---- the records: name in pred_dict and the pickle (and of the model attribute that switches the option on) -> ... ---------------
@@ -211,7 +270,9 @@ STEP_RECORDS = {"guard": ("guard_", ("count", "inliers", "rms", "verdict")),    
                 "st_fit": ("st_", ("inliers", "valid")),                         # int32
                 "rot_pool": ("rot_", ("inliers", "count")),                      # int32
                 # used int32, angle (degrees) / shift float32, and the predicted pose itself: (B,P,3,3), (B,P,3,1)
-                "motion": ("motion_", ("used", "angle", "shift", "rotation", "translation"))}
+                "motion": ("motion_", ("used", "angle", "shift", "rotation", "translation")),
+                # held / accepted int32, free = the frame's own scale float32, n = the frames in the mean after this one int32
+                "size": ("size_", ("held", "accepted", "free", "n"))}
 # The host loop's records, ONE (B,) int32 tensor per frame (None: a frame without) -> the key that wraps it in the pickle.
 # otf_thin: which trajectories' lists were thinned (its sum: the frame's thinned instances); depth_filter: the pixels set to 0
 LOOP_RECORDS = {"otf_thin": "thinned", "depth_filter": "removed"}
@@ -232,8 +293,9 @@ def commit_with_records(commit, records):
         for name, frames in records.items():
             prefix, keys = STEP_RECORDS[name]
             frames[i] = {k: npcs.pop(prefix + k) for k in keys}
-        if "motion" in records:
-            pose = {k: pose[k] for k in POSE_KEYS}      # a committed frame keeps the three keys; the prediction is in its record
+        if "motion" in records or "size" in records:
+            # a committed frame keeps the three keys; the prediction is in its record, the size state only in the travelling dict
+            pose = {k: pose[k] for k in POSE_KEYS}
         return npcs, pose
     return wrapped if records else commit
 

@@ -881,6 +881,51 @@ int captra_part_fit_st_ransac(int b, int p, int n, int sym, int b0, int num_hyps
                               const float *prev_trans, const int *sample_rank, unsigned long long seed, float *scale, float *trans,
                               int *valid, int *best, int *num_inliers, captra_stream_t stream);
 
+/* Holding a track's size (no reference counterpart: its step calls part_fit_st_no_ransac with given_scale = None hard-coded,
+ * networks.py:225-228): a rigid part's NOCS scale is a constant of the instance, so the track carries its running mean from frame to
+ * frame and, once it is established, fits the step's translation with THAT scale given.  One launch, one workgroup per (b, p).
+ *   state   : size_mean (B,P) f32, size_n (B,P) i32 (frames averaged), size_miss (B,P) i32 (finite frames rejected in a row) in,
+ *             mean_out / n_out / miss_out out.  A state whose n <= 0, or whose mean is not finite or not > 0, counts as EMPTY: n_in = 0
+ *             and mean_in = +0 (what then passes through): no NaN leaves through the state.
+ *   modes   : num_hyps = 0 PLAIN: the caller has run captra_part_fit_st_track and passes its outputs as scale_free_in (B,P),
+ *             trans_free_in (B,P,3), valid_free_in (B,P) i32 -- the FREE fit; sample_rank, seed, inlier_th, prev_* and the free
+ *             outputs are not read / written.  1 <= num_hyps <= 256 ROBUST: the three *_free_in are NULL and the kernel computes the
+ *             free fit itself, captra_part_fit_st_ransac on the same arguments (prev_scale / prev_trans rule included), written to
+ *             scale_free, trans_free, valid_free (required) and best, num_inliers (optional), bit for bit that entry's outputs -- the
+ *             launch REPLACES the step's captra_part_fit_st_ransac.
+ *   decision (thread 0, in double on the fp32 values as stored; every output rounded to fp32 once):
+ *             finite      = valid_free != 0 && isfinite(scale_free) && scale_free > 0
+ *             established = n_in >= min_frames
+ *             accept      = finite && (!established || (scale_free <= max_ratio mean_in && scale_free max_ratio >= mean_in))   (closed)
+ *             accept : k = min(n_in, max_frames - 1) (max_frames = 0: no cap); mean_out = fp32(mean_in + (scale_free - mean_in) / (k + 1)),
+ *                      with k = 0 scale_free bit for bit; n_out = k + 1; miss_out = 0.
+ *             reject : the state passes through bit for bit, except miss_out = miss_in + 1 when finite; with reset_after > 0 and
+ *                      miss_out >= reset_after the state RESTARTS from this frame: mean_out = scale_free, n_out = 1, miss_out = 0, and
+ *                      the frame counts as accepted (a size established from bad first frames would otherwise reject for ever).
+ *             held   = n_out >= min_frames && the sum of rot is finite.
+ *   not held: scale, trans, valid = the free fit's, bit for bit; held_best = held_inliers = 0.  The workgroup leaves there.
+ *   held    : scale = mean_out, trans from estimator E of captra_part_fit_st_ransac WITH THE SCALE GIVEN: s := mean_out in place of
+ *             <R', C> / (...), everything else -- centroids, sym = 1's in-plane angle from the moments, t = tb - s R' sb -- unchanged.
+ *             PLAIN : E-given over all members, by the refit's code and summation order with every member counted as an inlier;
+ *                     valid = count > 3 && t finite; held_inliers = count, held_best = 0.
+ *             ROBUST: E-given on the three-member samples (the free fit's own: sample_rank, or the same key with b0 + b), scored by
+ *                     the inlier test of that sym, the first best, E-given on its inliers; valid = count > 3 && inliers >= 3 && t
+ *                     finite; held_best / held_inliers = what was found.
+ *             A held fit that is not valid writes scale = mean_out, trans = the free fit's bit for bit, valid = 0.
+ *   record  : held (B,P) i32, accepted (B,P) i32 (required); held_best, held_inliers (B,P) i32 (NULL = not wanted).
+ * The shape limits of captra_part_fit_st_ransac with num_hyps = 0 allowed; these, sym outside {0, 1}, b0 < 0 or b0 > INT_MAX - b,
+ * min_frames < 1, max_ratio not finite or <= 1, max_frames < 0, reset_after < 0 (0 = not given: no cap / never), a NULL among labels,
+ * src, tgt, rot, the state's six, scale, trans, valid, held, accepted, plain mode without all three *_free_in, robust mode with any of
+ * them or without scale_free / trans_free / valid_free return -1 without a launch; b = 0 returns 0.  Outputs must not alias inputs. */
+int captra_part_fit_st_size(int b, int p, int n, int sym, int b0, int num_hyps, float inlier_th, const int *labels, const float *src,
+                            const float *tgt, int tgt_per_part, const float *tgt_mean, const float *rot, const float *prev_scale,
+                            const float *prev_trans, const int *sample_rank, unsigned long long seed, const float *scale_free_in,
+                            const float *trans_free_in, const int *valid_free_in, const float *size_mean, const int *size_n,
+                            const int *size_miss, int min_frames, float max_ratio, int max_frames, int reset_after, float *scale,
+                            float *trans, int *valid, float *scale_free, float *trans_free, int *valid_free, int *best, int *num_inliers,
+                            float *mean_out, int *n_out, int *miss_out, int *held, int *accepted, int *held_best, int *held_inliers,
+                            captra_stream_t stream);
+
 /* CoordinateNet read-out (networks.py:50 F.softmax(dim=1) + model.py:466 torch.max(seg, dim=-2)[1]) in one launch: logits (B,S,N),
  * S <= 8 -> seg (B,S,N) softmax (or NULL), labels (B,N) i32 = FIRST index of the largest logit (or NULL). */
 int captra_seg_softmax_argmax(int b, int s, int n, const float *logits, float *seg, int *labels, captra_stream_t stream);
