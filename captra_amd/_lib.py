@@ -88,6 +88,10 @@ _SIGNATURES = {
     "captra_crop_box": [_INT, _INT, _INT, C.c_double, _P, _P, _P, _P, _P, _P, _P],
     "captra_crop_box_det": [_INT, _INT, _INT, _INT, _INT, C.c_double] + [_P] * 11 + [_P],
     "captra_crop_ball_det": [_INT, _INT, _INT, _INT, _INT] + [_P] * 12 + [_P],
+    "captra_crop_box_cam": [_INT, _INT, _INT, C.c_double, _P, _P, _INT, _P, _P, _P, _P, _P, _P],
+    "captra_crop_box_det_cam": [_INT, _INT, _INT, _INT, _INT, C.c_double, _P, _P, _INT] + [_P] * 10 + [_P],
+    "captra_crop_ball_cam": [_INT, _INT, _INT, _INT, _P, _P, _P, _P, _P, _INT, _P, _P, _P, _P, _P, _P, _P],
+    "captra_crop_ball_det_cam": [_INT, _INT, _INT, _INT, _INT] + [_P] * 7 + [_INT] + [_P] * 6 + [_P],
     "captra_otf_candidates": [_INT, _INT, _INT, _INT, _P, _P, _P, _P, _P, _P],
     "captra_otf_finish": [_INT, _INT, _INT, _INT] + [_P] * 11 + [_P],
     "captra_otf_thin": [_INT, _INT, _INT, _INT, C.c_uint, C.c_ulonglong, _P, _P, _P, _P, _P],
@@ -95,6 +99,7 @@ _SIGNATURES = {
     "captra_otf_finish_thin": [_INT, _INT, _INT, _INT] + [_P] * 13 + [_P],
     "captra_depth_support_filter": [_INT] * 7 + [_P, _P, _P, _P],
     "captra_image_members": [_INT] * 6 + [_P] * 9 + [_P],
+    "captra_image_members_cam": [_INT] * 6 + [_P] * 3 + [_INT] + [_P] * 7 + [_P],
     "captra_sa_scale_pre": [_INT] * 8 + [_P] * 9 + [_P, _INT, _INT, _P],
     "captra_sa_scale_pre_pm": [_INT] * 8 + [_P] * 9 + [_P, _INT, _INT, _P],
     "captra_pointwise_mlp_pm": [_INT, _INT, _INT, _LL, _P, _P, _P, _INT, _P, _P],

@@ -9,6 +9,11 @@
 // Arithmetic is float64 like numpy's, written out operation by operation (no FMA contraction: the build runs with
 // -ffp-contract=off):  ray = Kinv (col, H - row, 1);  p = ray * z / ray_z;  p = (p_x, p_y, -p_z) * 0.001;
 // member  <=>  sqrt(((p - c)_x^2 + (p - c)_y^2) + (p - c)_z^2) <= radius.
+//
+// The camera model (include/captra_hip.h: captra_crop_ball_cam and its kin): the *_cam entry points take a table of cameras, (ncam,19)
+// doubles = K, K^-1, depth_unit per row, and one row index per trajectory; Kinv and 0.001 above become that row's Kinv and unit, the box
+// projection takes that row's K (its 1000.0 stays a constant: the projection is scale-free).  The kernels are templated on CAM; the
+// plain instantiations read `kinv` / `kmat` and the literal 0.001 as before.
 #include "common.h"
 
 #include <math.h>
@@ -16,12 +21,23 @@
 namespace {
 
 constexpr int CB_T = 1024;
+constexpr int CAM_ROW = 19;              // doubles per camera: K (9), K^-1 (9), depth_unit (1)
+
+// The camera row of trajectory i: cam_of[i] clamped into the table (memory safety only: the host wrapper builds cam_of).
+__device__ __forceinline__ const double *cam_row(const double *__restrict__ cams, const int *__restrict__ cam_of, int ncam, int i) {
+    int c = cam_of[i];
+    c = c < 0 ? 0 : (c < ncam ? c : ncam - 1);
+    return cams + (size_t)c * CAM_ROW;
+}
 
 // DET (captra_crop_ball_det): the instance mask of trajectory b is detection sel[b] of det_masks (B,ndet,h,w) -- the mask the detector
 // route selected (crop_box_det_kernel below) -- and mask_all's when sel[b] < 0 (no detection of the category: the reference keeps the
 // pre-fetched mask, nocs_data_process.py:217-218).  The three extra parameters come LAST and the plain instantiation does not touch
 // them: captra_crop_ball's instruction stream is what it was.
-template <bool DET>
+// CAM (captra_crop_ball_cam, captra_crop_ball_det_cam): Kinv and the depth unit of trajectory b are those of row cam_of[b] of cams -- one
+// row per workgroup, at a workgroup-uniform address: ten scalar loads in front of the pixel loop, nothing per pixel.  Again the three
+// parameters come last and the plain instantiations do not touch them (their unit is the literal 0.001).
+template <bool DET, bool CAM>
 __global__ __launch_bounds__(CB_T) void crop_ball_kernel(int h, int w, int cap, const int *__restrict__ depth_all,
                                                          const unsigned char *__restrict__ mask_all,
                                                          const int *__restrict__ box_all, const double *__restrict__ center_all,
@@ -29,7 +45,8 @@ __global__ __launch_bounds__(CB_T) void crop_ball_kernel(int h, int w, int cap, 
                                                          double *__restrict__ pts_all, unsigned char *__restrict__ obj_all,
                                                          int *__restrict__ pix_all, int *__restrict__ counts,
                                                          const unsigned char *__restrict__ det_masks, const int *__restrict__ sel_all,
-                                                         int ndet) {
+                                                         int ndet, int ncam, const double *__restrict__ cams,
+                                                         const int *__restrict__ cam_of) {
     __shared__ int wave_tot[2][16];
     const int b = blockIdx.x;
     const int *depth = depth_all + (size_t)b * h * w;
@@ -42,8 +59,16 @@ __global__ __launch_bounds__(CB_T) void crop_ball_kernel(int h, int w, int cap, 
     const double cx = center_all[b * 3 + 0], cy = center_all[b * 3 + 1], cz = center_all[b * 3 + 2];
     const double rad = radius_all[b];
     double k[9];
+    double unit = 0.001;
+    if constexpr (CAM) {
+        const double *__restrict__ cam = cam_row(cams, cam_of, ncam, b);
 #pragma unroll
-    for (int i = 0; i < 9; ++i) k[i] = kinv[i];
+        for (int i = 0; i < 9; ++i) k[i] = cam[9 + i];
+        unit = cam[18];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) k[i] = kinv[i];
+    }
     double *pts = pts_all + (size_t)b * cap * 3;
     unsigned char *obj = obj_all + (size_t)b * cap;
     int *pix = pix_all + (size_t)b * cap;
@@ -67,9 +92,9 @@ __global__ __launch_bounds__(CB_T) void crop_ball_kernel(int h, int w, int cap, 
                 const double ry = (k[3] * u + k[4] * v) + k[5];
                 const double rz = (k[6] * u + k[7] * v) + k[8];
                 const double z = (double)(float)d;                 // depth[idxs].astype(np.float32)
-                px = (rx * z / rz) * 0.001;
-                py = (ry * z / rz) * 0.001;
-                pz = -(rz * z / rz) * 0.001;
+                px = (rx * z / rz) * unit;
+                py = (ry * z / rz) * unit;
+                pz = -(rz * z / rz) * unit;
                 const double dx = px - cx, dy = py - cy, dz = pz - cz;
                 member = sqrt((dx * dx + dy * dy) + dz * dz) <= rad;
             }
@@ -130,11 +155,14 @@ __device__ __forceinline__ double crop_box_project(int h, int w, const double c[
     return r;
 }
 
+// CAM (captra_crop_box_cam): the projection of instance i with the K of row cam_of[i] of cams (the first 9 doubles of the row).
+template <bool CAM>
 __global__ void crop_box_kernel(int b, int h, int w, double radius_factor, const float *__restrict__ trans, const float *__restrict__ scale,
                                 const double *__restrict__ kmat, int *__restrict__ box, double *__restrict__ center,
-                                double *__restrict__ radius) {
+                                double *__restrict__ radius, int ncam, const double *__restrict__ cams, const int *__restrict__ cam_of) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= b) return;
+    if constexpr (CAM) kmat = cam_row(cams, cam_of, ncam, i);
     const double c[3] = {(double)trans[i * 3 + 0], (double)trans[i * 3 + 1], (double)trans[i * 3 + 2]};
     int bx[4];
     const double r = crop_box_project(h, w, c, radius_factor * (double)scale[i], kmat, bx);
@@ -157,13 +185,17 @@ __global__ void crop_box_kernel(int b, int h, int w, double radius_factor, const
 // Outside the reference's contract: a detection whose union with the box is 0 counts as IoU 0 (numpy: 0/0 = NaN); a growth step that
 // does not enlarge the radius -- NaN, inf, <= 0, or a subnormal that 1.2 x rounds back to itself -- ends the loop at once (the
 // reference would not terminate there).
+// CAM (captra_crop_box_det_cam): as crop_box_kernel<true>; the row is the wave's.
+template <bool CAM>
 __global__ __launch_bounds__(64) void crop_box_det_kernel(int h, int w, int ndet, int category, double radius_factor,
                                                           const float *__restrict__ trans, const float *__restrict__ scale,
                                                           const double *__restrict__ kmat, const int *__restrict__ det_boxes,
                                                           const int *__restrict__ det_class, const int *__restrict__ det_count,
                                                           int *__restrict__ box, double *__restrict__ center, double *__restrict__ radius,
-                                                          double *__restrict__ radius_raw, int *__restrict__ sel) {
+                                                          double *__restrict__ radius_raw, int *__restrict__ sel, int ncam,
+                                                          const double *__restrict__ cams, const int *__restrict__ cam_of) {
     const int i = blockIdx.x, lane = threadIdx.x;
+    if constexpr (CAM) kmat = cam_row(cams, cam_of, ncam, i);
     const double c[3] = {(double)trans[i * 3 + 0], (double)trans[i * 3 + 1], (double)trans[i * 3 + 2]};
     double r = radius_factor * (double)scale[i];
     int cnt = det_count[i];
@@ -323,8 +355,8 @@ extern "C" int captra_crop_box(int b, int h, int w, double radius_factor, const 
                                int *box, double *center, double *radius, captra_stream_t stream) {
     if (b < 0 || h < 1 || w < 1) return -1;
     if (b == 0) return 0;
-    CAPTRA_LAUNCH("crop_ball", crop_box_kernel, dim3((b + 63) / 64), dim3(64), 0, (hipStream_t)stream, b, h, w, radius_factor, trans,
-                  scale, kmat, box, center, radius);
+    CAPTRA_LAUNCH("crop_ball", crop_box_kernel<false>, dim3((b + 63) / 64), dim3(64), 0, (hipStream_t)stream, b, h, w, radius_factor, trans,
+                  scale, kmat, box, center, radius, 0, (const double *)nullptr, (const int *)nullptr);
     return captra_last_error();
 }
 
@@ -333,8 +365,9 @@ extern "C" int captra_crop_ball(int b, int h, int w, int cap, const int *depth, 
                                 unsigned char *obj, int *pix, int *counts, captra_stream_t stream) {
     if (b < 0 || h < 1 || w < 1 || cap < 1) return -1;
     if (b == 0) return 0;
-    CAPTRA_LAUNCH("crop_ball", crop_ball_kernel<false>, dim3(b), dim3(CB_T), 0, (hipStream_t)stream, h, w, cap, depth, mask, box,
-                  center, radius, kinv, pts, obj, pix, counts, (const unsigned char *)nullptr, (const int *)nullptr, 0);
+    CAPTRA_LAUNCH("crop_ball", (crop_ball_kernel<false, false>), dim3(b), dim3(CB_T), 0, (hipStream_t)stream, h, w, cap, depth, mask, box,
+                  center, radius, kinv, pts, obj, pix, counts, (const unsigned char *)nullptr, (const int *)nullptr, 0, 0,
+                  (const double *)nullptr, (const int *)nullptr);
     return captra_last_error();
 }
 
@@ -345,8 +378,9 @@ extern "C" int captra_crop_box_det(int b, int h, int w, int ndet, int category, 
                                    double *center, double *radius, double *radius_raw, int *sel, captra_stream_t stream) {
     if (b < 0 || h < 1 || w < 1 || ndet < 0) return -1;
     if (b == 0) return 0;
-    CAPTRA_LAUNCH("crop_ball", crop_box_det_kernel, dim3(b), dim3(64), 0, (hipStream_t)stream, h, w, ndet, category, radius_factor, trans,
-                  scale, kmat, det_boxes, det_class, det_count, box, center, radius, radius_raw, sel);
+    CAPTRA_LAUNCH("crop_ball", crop_box_det_kernel<false>, dim3(b), dim3(64), 0, (hipStream_t)stream, h, w, ndet, category, radius_factor, trans,
+                  scale, kmat, det_boxes, det_class, det_count, box, center, radius, radius_raw, sel, 0, (const double *)nullptr,
+                  (const int *)nullptr);
     return captra_last_error();
 }
 
@@ -357,8 +391,56 @@ extern "C" int captra_crop_ball_det(int b, int h, int w, int cap, int ndet, cons
                                     captra_stream_t stream) {
     if (b < 0 || h < 1 || w < 1 || cap < 1 || ndet < 0) return -1;
     if (b == 0) return 0;
-    CAPTRA_LAUNCH("crop_ball", crop_ball_kernel<true>, dim3(b), dim3(CB_T), 0, (hipStream_t)stream, h, w, cap, depth, mask, box,
-                  center, radius, kinv, pts, obj, pix, counts, det_masks, sel, ndet);
+    CAPTRA_LAUNCH("crop_ball", (crop_ball_kernel<true, false>), dim3(b), dim3(CB_T), 0, (hipStream_t)stream, h, w, cap, depth, mask, box,
+                  center, radius, kinv, pts, obj, pix, counts, det_masks, sel, ndet, 0, (const double *)nullptr, (const int *)nullptr);
+    return captra_last_error();
+}
+
+// ---- the camera model: the four calls above with a camera per trajectory (include/captra_hip.h, "The CAMERA MODEL") -----------------
+extern "C" int captra_crop_box_cam(int b, int h, int w, double radius_factor, const float *trans, const float *scale, int ncam,
+                                   const double *cams, const int *cam_of, int *box, double *center, double *radius, captra_stream_t stream) {
+    if (b < 0 || h < 1 || w < 1 || ncam < 1) return -1;
+    if (b == 0) return 0;
+    if (cams == nullptr || cam_of == nullptr) return -1;
+    CAPTRA_LAUNCH("crop_ball", crop_box_kernel<true>, dim3((b + 63) / 64), dim3(64), 0, (hipStream_t)stream, b, h, w, radius_factor, trans,
+                  scale, (const double *)nullptr, box, center, radius, ncam, cams, cam_of);
+    return captra_last_error();
+}
+
+extern "C" int captra_crop_box_det_cam(int b, int h, int w, int ndet, int category, double radius_factor, const float *trans,
+                                       const float *scale, int ncam, const double *cams, const int *cam_of, const int *det_boxes,
+                                       const int *det_class, const int *det_count, int *box, double *center, double *radius,
+                                       double *radius_raw, int *sel, captra_stream_t stream) {
+    if (b < 0 || h < 1 || w < 1 || ndet < 0 || ncam < 1) return -1;
+    if (b == 0) return 0;
+    if (cams == nullptr || cam_of == nullptr) return -1;
+    CAPTRA_LAUNCH("crop_ball", crop_box_det_kernel<true>, dim3(b), dim3(64), 0, (hipStream_t)stream, h, w, ndet, category, radius_factor,
+                  trans, scale, (const double *)nullptr, det_boxes, det_class, det_count, box, center, radius, radius_raw, sel, ncam, cams,
+                  cam_of);
+    return captra_last_error();
+}
+
+extern "C" int captra_crop_ball_cam(int b, int h, int w, int cap, const int *depth, const unsigned char *mask, const int *box,
+                                    const double *center, const double *radius, int ncam, const double *cams, const int *cam_of,
+                                    double *pts, unsigned char *obj, int *pix, int *counts, captra_stream_t stream) {
+    if (b < 0 || h < 1 || w < 1 || cap < 1 || ncam < 1) return -1;
+    if (b == 0) return 0;
+    if (cams == nullptr || cam_of == nullptr) return -1;
+    CAPTRA_LAUNCH("crop_ball", (crop_ball_kernel<false, true>), dim3(b), dim3(CB_T), 0, (hipStream_t)stream, h, w, cap, depth, mask, box,
+                  center, radius, (const double *)nullptr, pts, obj, pix, counts, (const unsigned char *)nullptr, (const int *)nullptr, 0,
+                  ncam, cams, cam_of);
+    return captra_last_error();
+}
+
+extern "C" int captra_crop_ball_det_cam(int b, int h, int w, int cap, int ndet, const int *depth, const unsigned char *mask,
+                                        const unsigned char *det_masks, const int *sel, const int *box, const double *center,
+                                        const double *radius, int ncam, const double *cams, const int *cam_of, double *pts,
+                                        unsigned char *obj, int *pix, int *counts, captra_stream_t stream) {
+    if (b < 0 || h < 1 || w < 1 || cap < 1 || ndet < 0 || ncam < 1) return -1;
+    if (b == 0) return 0;
+    if (cams == nullptr || cam_of == nullptr) return -1;
+    CAPTRA_LAUNCH("crop_ball", (crop_ball_kernel<true, true>), dim3(b), dim3(CB_T), 0, (hipStream_t)stream, h, w, cap, depth, mask, box,
+                  center, radius, (const double *)nullptr, pts, obj, pix, counts, det_masks, sel, ndet, ncam, cams, cam_of);
     return captra_last_error();
 }
 

@@ -48,12 +48,17 @@ __device__ __forceinline__ int im_classify(const ImImage &im, int t, int r, int 
     return inside ? (d > 0 ? 1 : 2) : 0;
 }
 
+// CAM (captra_image_members_cam; include/captra_hip.h, "The CAMERA MODEL"): Kinv and the depth unit of image i are those of row cam_of[i]
+// (clamped into the table) of cams (ncam,19) = K, K^-1, depth_unit -- one row per workgroup, read once in front of pass 2.  The three
+// parameters come last and the plain instantiation does not touch them: captra_image_members' instruction stream is what it was.
+template <bool CAM>
 __global__ __launch_bounds__(IM_T) void image_members_kernel(int h, int w, int cap, int border, int negate_z, int split, int share,
                                                              const int *__restrict__ depth_all, const unsigned char *__restrict__ mask_all,
                                                              const unsigned char *__restrict__ coord_all, const double *__restrict__ kinv,
                                                              float *__restrict__ src_all, float *__restrict__ tgt_all,
                                                              int *__restrict__ labels_all, int *__restrict__ pix_all,
-                                                             int *__restrict__ counts) {
+                                                             int *__restrict__ counts, int ncam, const double *__restrict__ cams,
+                                                             const int *__restrict__ cam_of) {
     __shared__ int acc[3];
     __shared__ int wave_tot[2][IM_T / 64];
     const int img = blockIdx.x / split, g = blockIdx.x - img * split;
@@ -133,8 +138,18 @@ __global__ __launch_bounds__(IM_T) void image_members_kernel(int h, int w, int c
 
     // ---- pass 2: this workgroup's share, in order
     double k9[9];
+    double unit = 0.001;
+    if constexpr (CAM) {
+        int ci = cam_of[img];
+        ci = ci < 0 ? 0 : (ci < ncam ? ci : ncam - 1);
+        const double *__restrict__ cam = cams + (size_t)ci * 19;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) k9[i] = kinv[i];
+        for (int i = 0; i < 9; ++i) k9[i] = cam[9 + i];
+        unit = cam[18];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) k9[i] = kinv[i];
+    }
     const unsigned char *__restrict__ coord = coord_all + (size_t)img * hw * 3;
     int base = before, it = 0;
     for (long long t0 = t_lo; t0 < t_hi; t0 += IM_T, ++it) {        // (64-bit: hw may be INT_MAX)
@@ -166,9 +181,9 @@ __global__ __launch_bounds__(IM_T) void image_members_kernel(int h, int w, int c
                 const double ry = (k9[3] * u + k9[4] * v) + k9[5];
                 const double rz = (k9[6] * u + k9[7] * v) + k9[8];
                 const double z = (double)(float)d;                   // captra_crop_ball's: depth[idxs].astype(np.float32)
-                tgt[s] = (float)((rx * z / rz) * 0.001);
-                tgt[(size_t)cap + s] = (float)((ry * z / rz) * 0.001);
-                tgt[(size_t)2 * cap + s] = (float)(-(rz * z / rz) * 0.001);
+                tgt[s] = (float)((rx * z / rz) * unit);
+                tgt[(size_t)cap + s] = (float)((ry * z / rz) * unit);
+                tgt[(size_t)2 * cap + s] = (float)(-(rz * z / rz) * unit);
                 const unsigned char *__restrict__ q = coord + (size_t)t * 3;
                 const double n0 = (double)q[0] / 255.0 - 0.5, n1 = (double)q[1] / 255.0 - 0.5, n2 = (double)q[2] / 255.0 - 0.5;
                 src[s] = (float)n0;
@@ -188,15 +203,19 @@ CAPTRA_KNOB int g_im_split = 0;          // measurement knob: workgroups per ima
 
 extern "C" void captra_image_members_set_split(int n) { g_im_split = n; }
 
-extern "C" int captra_image_members(int b, int h, int w, int cap, int border, int negate_z, const int *depth, const unsigned char *mask,
-                                    const unsigned char *coord, const double *kinv, float *src, float *tgt, int *labels, int *pix,
-                                    int *counts, captra_stream_t stream) {
+// The launch of both entry points: kinv (CAM = false) or the camera table (CAM = true).
+template <bool CAM>
+static int image_members_launch(int b, int h, int w, int cap, int border, int negate_z, const int *depth, const unsigned char *mask,
+                                const unsigned char *coord, const double *kinv, int ncam, const double *cams, const int *cam_of, float *src,
+                                float *tgt, int *labels, int *pix, int *counts, captra_stream_t stream) {
     if (b < 0 || h < 0 || w < 0 || cap < 1 || border < 0 || border > 3) return -1;
     if ((long long)h * (long long)w > (long long)INT_MAX) return -1;
+    if (CAM && ncam < 1) return -1;
     if (b == 0 || h == 0 || w == 0) return 0;
-    if (depth == nullptr || mask == nullptr || coord == nullptr || kinv == nullptr || src == nullptr || tgt == nullptr || labels == nullptr ||
-        pix == nullptr || counts == nullptr)
+    if (depth == nullptr || mask == nullptr || coord == nullptr || src == nullptr || tgt == nullptr || labels == nullptr || pix == nullptr ||
+        counts == nullptr)
         return -1;
+    if (CAM ? (cams == nullptr || cam_of == nullptr) : kinv == nullptr) return -1;
     const int hw = h * w;
     // workgroups per image: the device filled twice, a share of at least 4096 pixels (the knob: any number up to a pixel per workgroup)
     long long split = g_im_split > 0 ? g_im_split : (2LL * captra_device_cus() + b - 1) / b;
@@ -205,7 +224,21 @@ extern "C" int captra_image_members(int b, int h, int w, int cap, int border, in
     split = split < INT_MAX / b ? split : INT_MAX / b;               // (the grid is one-dimensional: images x split)
     split = split > 1 ? split : 1;
     const int share = (int)((hw + split - 1) / split);
-    CAPTRA_LAUNCH("image_members", image_members_kernel, dim3((unsigned)(b * split)), dim3(IM_T), 0, (hipStream_t)stream, h, w, cap, border,
-                  negate_z, (int)split, share, depth, mask, coord, kinv, src, tgt, labels, pix, counts);
+    CAPTRA_LAUNCH("image_members", image_members_kernel<CAM>, dim3((unsigned)(b * split)), dim3(IM_T), 0, (hipStream_t)stream, h, w, cap, border,
+                  negate_z, (int)split, share, depth, mask, coord, kinv, src, tgt, labels, pix, counts, ncam, cams, cam_of);
     return captra_last_error();
+}
+
+extern "C" int captra_image_members(int b, int h, int w, int cap, int border, int negate_z, const int *depth, const unsigned char *mask,
+                                    const unsigned char *coord, const double *kinv, float *src, float *tgt, int *labels, int *pix,
+                                    int *counts, captra_stream_t stream) {
+    return image_members_launch<false>(b, h, w, cap, border, negate_z, depth, mask, coord, kinv, 0, nullptr, nullptr, src, tgt, labels, pix,
+                                       counts, stream);
+}
+
+extern "C" int captra_image_members_cam(int b, int h, int w, int cap, int border, int negate_z, const int *depth, const unsigned char *mask,
+                                        const unsigned char *coord, int ncam, const double *cams, const int *cam_of, float *src, float *tgt,
+                                        int *labels, int *pix, int *counts, captra_stream_t stream) {
+    return image_members_launch<true>(b, h, w, cap, border, negate_z, depth, mask, coord, nullptr, ncam, cams, cam_of, src, tgt, labels,
+                                      pix, counts, stream);
 }

@@ -196,6 +196,15 @@ def image_fit_table(name: str, data: dict) -> list:
     return [f"{name}: members {r['members']}; used {r['used']}; holes {r['holes']}; inliers {r['inliers']}; valid {'yes' if r['valid'] else 'no'}"]
 
 
+def camera_table(name: str, data: dict) -> list:
+    """The camera of one result pickle's trajectory (present when the run had a camera: the `camera` section or the frames' own): one
+    line with fx, fy, cx, cy (and the skew when there is one) and the depth unit in metres per count."""
+    K = np.asarray(data["camera"]["K"], np.float64).reshape(-1, 3, 3)[0]
+    unit = float(np.asarray(data["camera"]["depth_unit"], np.float64).reshape(-1)[0])
+    skew = f"; skew {K[0, 1]:g}" if K[0, 1] != 0 else ""
+    return [f"{name}: fx {K[0, 0]:g}; fy {K[1, 1]:g}; cx {K[0, 2]:g}; cy {K[1, 2]:g}{skew}; depth unit {unit:g} m"]
+
+
 # the options' records a result pickle may carry, in the order they are printed: (pickle key, its table, the heading -- {tests}: the
 # inlier tests the runs' guards used)
 RECORD_TABLES = (
@@ -207,6 +216,7 @@ RECORD_TABLES = (
     ("otf_thin", otf_thin_table, "re-crop lists thinned on the device (track_cfg/otf_thin), frames per trajectory:"),
     ("depth_filter", depth_filter_table, "flying depth pixels removed at upload (track_cfg/depth_filter), per trajectory:"),
     ("image_fit", image_fit_table, "first pose fitted from frame 0's images (init_frame/image_fit), per trajectory:"),
+    ("camera", camera_table, "camera (camera / the frames' own), per trajectory:"),
 )
 
 

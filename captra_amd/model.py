@@ -134,6 +134,12 @@ class EvalTrackModel(BaseModel):
         self.otf_thin = O.otf_thin_cfg(cfg)                                # the re-crop's over-long lists thinned on the device
         self._otf_thin_rec = {}             # frame -> {first trajectory of a slice: its thinned flags (b,) int32 on the device}
         self.depth_filter = O.depth_filter_cfg(cfg)                        # flying pixels out of every uploaded depth image
+        # the camera model: the configuration's camera, and per batch (set_data) the trajectories' cameras as PERSISTENT device tensors
+        # -- `camera` = (table (C,19) float64, cam_of (B,) int32), what the *_cam entry points read in every frame -- and on the host
+        # for the pickle; None = no camera anywhere: the plain entry points, no tensor
+        self.camera_cfg = O.camera_cfg(cfg)
+        self.camera = None
+        self._camera_host = None
         self.radius = cfg["data_radius"]
         self.det_category = cfg["obj_category"]          # nocs2d_label: the class id the frame's detections are matched against
         self._det_missing_logged = False
@@ -236,7 +242,39 @@ class EvalTrackModel(BaseModel):
             out["labels"] = frame["labels"].long().to(self.device)
         return out
 
+    def _set_cameras(self, data):
+        """The batch's cameras (track_options.trajectory_cameras: frame 0's own, then the configuration's, then none) onto the device,
+        once; a later frame whose camera differs from frame 0's is an error -- a camera belongs to a trajectory."""
+        self.camera = self._camera_host = None
+        pres = [f["meta"].get("pre_fetched") for f in data]
+        if not pres or pres[0] is None or not (self.nocs_otf or self.image_fit is not None):
+            return
+        depth = pres[0]["depth"]
+        if isinstance(depth, (list, tuple)):
+            sizes = sorted({tuple(np.shape(d)[-2:]) for d in depth})
+            if len(sizes) > 1:
+                raise ValueError(f"the images of one batch share their size H x W; this batch has {sizes} (several image sizes in one batch are "
+                                 "outside the camera model: batch the trajectories by image size)")
+        B = len(depth)
+        cams = O.trajectory_cameras(pres[0].get("camera"), self.camera_cfg, B)
+        for i, pre in enumerate(pres[1:], 1):
+            if pre is None or pre.get("camera") is None:
+                continue                    # (a later frame need not repeat it)
+            # (compared by bytes, not parsed again: a camera that equals frame 0's is as valid as frame 0's)
+            same = pres[0].get("camera") is not None and all(
+                pre["camera"].get(k) is pres[0]["camera"][k] or (pre["camera"].get(k) is not None and
+                    np.asarray(torch.as_tensor(pre["camera"][k]).cpu().numpy(), np.float64).tobytes() == cams[k].tobytes()) for k in ("K", "depth_unit"))
+            if not same:
+                raise ValueError(f"frame {i}'s camera (meta['pre_fetched']['camera']) differs from frame 0's: a camera belongs to a trajectory "
+                                 "and is constant over its frames")
+        if cams is None:
+            return
+        from .nocs_otf import camera_table
+        self.camera = camera_table(cams["K"], cams["depth_unit"], self.device)
+        self._camera_host = cams
+
     def set_data(self, data):
+        self._set_cameras(data)
         self.feed_dict = [self._convert_pose_frame(f, i == 0) for i, f in enumerate(data)]
         self.npcs_feed_dict = [self._convert_npcs_frame(f) for f in data]
 
@@ -300,7 +338,7 @@ class EvalTrackModel(BaseModel):
                            "coordinate image)")
         cfg = self.image_fit
         mem = image_members(pre["depth"].contiguous(), pre["mask"].contiguous(), pre["coord"], cap=cfg["cap"], border=cfg["border"],
-                            negate_z=cfg["negate_z"])
+                            negate_z=cfg["negate_z"], cameras=self.camera)
         rot, scale, trans, valid, info = part_fit_ransac_cn(mem["labels"], mem["src"], mem["tgt"], num_hyps=self.fit_init_cfg["num_hyps"],
                                                             inlier_th=self.fit_init_cfg["inlier_th"], seed=self.fit_init_cfg["seed"],
                                                             yaxis_only=self.fit_init_yaxis)
@@ -578,11 +616,13 @@ class EvalTrackModel(BaseModel):
         # track_cfg/otf_thin: keyed by the trajectory's place in the whole batch and the frame, so that a lane draws what the whole
         # batch draws and a replayed frame what its first run drew
         thin = None if self.otf_thin is None else (self.otf_thin["seed"], i, sl.start or 0)
+        # the camera model: the table whole, cam_of sliced with the lane exactly as the depth images are
+        cameras = None if self.camera is None else (self.camera[0], self.camera[1][sl])
         if (OTF_POSE_ON_DEVICE or det is not None) and depth.is_cuda and trans_d.dtype == torch.float32 and scale_d.dtype == torch.float32:
             # the crop's box / centre / radius derived on the device from the pose (captra_crop_box): no round trip for the pose
             # (the detector route exists in this form only: its selection is captra_crop_box_det)
             full = full_data_batch_arrays(depth, mask, None, None, gt64, N, stacked=True, pose_dev=(trans_d, scale_d, float(self.radius)), gt_dev=gtd,
-                                          defer=defer, mean=npcs["points_mean"][sl], det=det, thin=thin)
+                                          defer=defer, mean=npcs["points_mean"][sl], det=det, thin=thin, cameras=cameras)
             if thin is not None:
                 self._otf_thin_rec.setdefault(i, {})[sl.start or 0] = full["_thinned"]     # (a replay of the frame puts its own in place)
             if defer is not None:
@@ -595,7 +635,7 @@ class EvalTrackModel(BaseModel):
         else:
             defer = None
             cs = to_host(torch.cat([trans_d, scale_d.reshape(b, 1)], dim=1).double())
-            full = full_data_batch_arrays(depth, mask, cs[:, :3], self.radius * cs[:, 3], gt64, N, stacked=True)
+            full = full_data_batch_arrays(depth, mask, cs[:, :3], self.radius * cs[:, 3], gt64, N, stacked=True, cameras=cameras)
         points = (full["points"].float() - npcs["points_mean"][sl].reshape(b, 1, 3)).transpose(1, 2).contiguous()
         return points, full["labels"].contiguous(), full["nocs"].float().transpose(1, 2).contiguous()
 
@@ -845,6 +885,8 @@ class EvalTrackModel(BaseModel):
             self.pred_dict["depth_filter"] = [f.get("depth_filter_removed") for f in feed]       # (None: a frame without depth)
         if self.image_fit is not None:
             self.pred_dict["image_fit"] = self._image_fit_rec
+        if self._camera_host is not None:
+            self.pred_dict["camera"] = self._camera_host
         self.check_l1_stream()
         if save:
             self._save(list(map(_frame_names, feed)))

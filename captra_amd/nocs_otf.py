@@ -46,6 +46,84 @@ def to_device(a, dev, dtype=None) -> torch.Tensor:
 NOCS_REAL_INTRINSICS = np.array([[591.0125, 0.0, 322.525], [0.0, 590.16775, 244.11084], [0.0, 0.0, 1.0]])   # nocs_data_process.py:20
 
 
+NOCS_CAMERA_INTRINSICS = np.array([[577.5, 0.0, 319.5], [0.0, 577.5, 239.5], [0.0, 0.0, 1.0]])             # get_gt_poses.py:100-102 (CAMERA25)
+CAMERA_PRESETS = {"nocs_real": (NOCS_REAL_INTRINSICS, 0.001), "nocs_camera": (NOCS_CAMERA_INTRINSICS, 0.001)}
+CAM_ROW = 19              # doubles per row of a camera table: K row-major (9), K^-1 row-major (9), depth_unit (1)
+
+
+def check_camera(K, depth_unit, prefix: str = "camera/") -> tuple:
+    """A camera as (K (3,3) float64, depth_unit float), or a ValueError that names the entry outside the model (`prefix`: where the
+    caller read it): K finite with last row 0 0 1 and fx, fy > 0; depth_unit = metres per depth count, finite and > 0."""
+    K = np.asarray(K, np.float64)
+    if K.shape != (3, 3):
+        raise ValueError(f"{prefix}K must be a 3x3 matrix, got shape {K.shape}")
+    for key, (r, c) in (("fx", (0, 0)), ("skew", (0, 1)), ("cx", (0, 2)), ("fy", (1, 1)), ("cy", (1, 2))):
+        if not np.isfinite(K[r, c]):
+            raise ValueError(f"{prefix}{key} must be finite, got {K[r, c]!r}")
+    for key, v in (("fx", K[0, 0]), ("fy", K[1, 1])):
+        if not v > 0:
+            raise ValueError(f"{prefix}{key} must be > 0, got {v!r}")
+    if not np.isfinite(K[1, 0]) or K[1, 0] != 0.0:
+        raise ValueError(f"{prefix}K[1][0] must be 0 (the model has one skew term, K[0][1]), got {K[1, 0]!r}")
+    if not np.array_equal(K[2], [0.0, 0.0, 1.0]):
+        raise ValueError(f"{prefix}K's last row must be 0 0 1, got {K[2].tolist()}")
+    try:
+        unit = float(depth_unit)
+    except (TypeError, ValueError):
+        raise ValueError(f"{prefix}depth_unit must be a number (metres per depth count), got {depth_unit!r}") from None
+    if not (np.isfinite(unit) and unit > 0):
+        raise ValueError(f"{prefix}depth_unit must be finite and > 0 (metres per depth count), got {depth_unit!r}")
+    return K, unit
+
+
+def camera_rows(K, depth_unit, prefix: str = "camera/") -> tuple:
+    """Per-trajectory cameras K (B,3,3), depth_unit (B,) -> (table (C,19) float64, cam_of (B,) int32) on the HOST: the cameras
+    de-duplicated by their bytes (K and unit), in order of first appearance; row = K, K^-1 (by _kinv), depth_unit."""
+    K = np.asarray(K, np.float64)
+    if K.ndim != 3 or K.shape[1:] != (3, 3):
+        raise ValueError(f"{prefix}K must be (B,3,3), one matrix per trajectory, got shape {K.shape}")
+    unit = np.asarray(depth_unit, np.float64).reshape(-1)
+    if unit.shape[0] != K.shape[0]:
+        raise ValueError(f"{prefix}depth_unit must be (B,) with B = {K.shape[0]} as K, got shape {np.shape(depth_unit)}")
+    rows, index, cam_of = [], {}, np.empty(K.shape[0], np.int32)
+    for b in range(K.shape[0]):
+        Kb, ub = check_camera(K[b], unit[b], prefix)
+        key = Kb.tobytes() + np.float64(ub).tobytes()
+        if key not in index:
+            index[key] = len(rows)
+            rows.append(np.concatenate([Kb.reshape(9), _kinv(Kb), [ub]]))
+        cam_of[b] = index[key]
+    table = np.stack(rows) if rows else np.zeros((0, CAM_ROW), np.float64)
+    return np.ascontiguousarray(table, np.float64), cam_of
+
+
+def camera_table(K, depth_unit, dev, prefix: str = "camera/") -> tuple:
+    """The `cameras` argument of full_data_batch_arrays / image_members from per-trajectory K (B,3,3) and depth_unit (B,): camera_rows'
+    table and cam_of as device tensors, in ONE upload (the int32 indices ride behind the doubles)."""
+    table, cam_of = camera_rows(K, depth_unit, prefix)
+    C, B = table.shape[0], cam_of.shape[0]
+    blob = np.empty(8 * CAM_ROW * C + 4 * B, np.uint8)
+    blob[:8 * CAM_ROW * C].view(np.float64)[:] = table.reshape(-1)
+    blob[8 * CAM_ROW * C:].view(np.int32)[:] = cam_of
+    d = to_device(blob, dev)
+    return d[:8 * CAM_ROW * C].view(torch.float64).view(C, CAM_ROW), d[8 * CAM_ROW * C:].view(torch.int32)
+
+
+def _check_cameras(cameras, B: int, dev) -> tuple:
+    """(table, cam_of) as the *_cam entry points read them, or a ValueError."""
+    table, cam_of = cameras
+    if (not torch.is_tensor(table) or table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != CAM_ROW or table.shape[0] < 1
+            or not table.is_contiguous()):
+        raise ValueError(f"cameras: the table is a contiguous float64 tensor (C,{CAM_ROW}) with C >= 1 (camera_table builds it), got "
+                         f"{getattr(table, 'dtype', type(table))} {tuple(getattr(table, 'shape', ()))}")
+    if not torch.is_tensor(cam_of) or cam_of.dtype != torch.int32 or tuple(cam_of.shape) != (B,):
+        raise ValueError(f"cameras: cam_of is an int32 tensor (B,) with B = {B}, one camera row per trajectory, got "
+                         f"{getattr(cam_of, 'dtype', type(cam_of))} {tuple(getattr(cam_of, 'shape', ()))}")
+    if table.device != dev or cam_of.device != dev:
+        raise ValueError(f"cameras: the table and cam_of live on the frames' device {dev}, got {table.device} and {cam_of.device}")
+    return table, cam_of.contiguous()
+
+
 def proj_corners(height: int, width: int, center, radius: float, intrinsics=NOCS_REAL_INTRINSICS) -> np.ndarray:
     """Image-space bounding box [[row_min, col_min], [row_max, col_max]] (inclusive, clamped) of the axis-aligned cube of
     half-size max(radius, 0.05) around `center` (camera frame, metres, looking down -z); nocs_data_process.py:136-148."""
@@ -106,11 +184,12 @@ def _device_fps(points_f32: torch.Tensor, num: int) -> torch.Tensor:
 
 
 def crop_candidates(depth: torch.Tensor, mask: torch.Tensor, center, radius: float, num_points: int,
-                    intrinsics=NOCS_REAL_INTRINSICS, _depth_retry: int = 0):
+                    intrinsics=NOCS_REAL_INTRINSICS, _depth_retry: int = 0, depth_unit: float = 0.001):
     """Everything of the crop BEFORE the furthest-point sampling (nocs_data_process.py:92-109, 151-163;
     data_utils.py:146-152): -> (pts (n,3) float64 back-projected pixels, raw_mask (n,) bool, idx (c,) long = the ball
     members, list-doubled up to num_points, perm (5*num_points,) long or None = the thinning of an over-long list).
-    The cloud handed to the sampler is pts[idx] (or pts[idx][perm]) as float32."""
+    The cloud handed to the sampler is pts[idx] (or pts[idx][perm]) as float32.  depth_unit: metres per depth count (the
+    camera model; 0.001 = the reference's millimetres)."""
     H, W = depth.shape
     dev = depth.device
     box = proj_corners(H, W, center, radius, intrinsics)
@@ -123,7 +202,7 @@ def crop_candidates(depth: torch.Tensor, mask: torch.Tensor, center, radius: flo
     xyz = (kinv @ grid).t()                                        # (n,3) float64
     z = depth[rows, cols].float().double()
     pts = xyz * z[:, None] / xyz[:, 2:3]
-    pts = torch.stack([pts[:, 0], pts[:, 1], -pts[:, 2]], dim=1) * 0.001
+    pts = torch.stack([pts[:, 0], pts[:, 1], -pts[:, 2]], dim=1) * float(depth_unit)
     raw_mask = mask[rows, cols].bool()
 
     c = torch.as_tensor(np.asarray(center, np.float64).reshape(1, 3), device=dev)
@@ -140,7 +219,7 @@ def crop_candidates(depth: torch.Tensor, mask: torch.Tensor, center, radius: flo
     if idx.numel() == 0:
         if _depth_retry > 20:
             raise RuntimeError("crop_ball_from_depth: no valid depth pixel anywhere near the predicted centre")
-        return crop_candidates(depth, mask, center, float(radius) * 1.2, num_points, intrinsics, _depth_retry + 1)
+        return crop_candidates(depth, mask, center, float(radius) * 1.2, num_points, intrinsics, _depth_retry + 1, depth_unit)
     while idx.numel() < num_points:
         idx = torch.cat([idx, idx])
     perm = None
@@ -256,7 +335,8 @@ DET_KEYS = ("det_boxes", "det_class", "det_count", "det_masks")
 
 def check_depth_filter_params(window, abs_mm, rel_permille, min_support, prefix: str = "") -> tuple:
     """The four parameters of captra_depth_support_filter as ints, or a ValueError that names the one outside the kernel's range
-    (`prefix`: where the caller read them, e.g. 'track_cfg/depth_filter/')."""
+    (`prefix`: where the caller read them, e.g. 'track_cfg/depth_filter/').  abs_mm is in DEPTH COUNTS: millimetres for a millimetre
+    sensor (the name's origin), `abs_mm * depth_unit` metres under a camera whose depth unit is not 0.001."""
     vals = {}
     for key, v in (("window", window), ("abs_mm", abs_mm), ("rel_permille", rel_permille), ("min_support", min_support)):
         if isinstance(v, bool) or int(v) != v:
@@ -312,7 +392,7 @@ def check_image_fit_params(cap, border, prefix: str = "") -> tuple:
 
 
 def image_members(depth: torch.Tensor, mask: torch.Tensor, coord: torch.Tensor, intrinsics=NOCS_REAL_INTRINSICS, cap: int = IMAGE_FIT_CAP,
-                  border: int = 0, negate_z: bool = False) -> dict:
+                  border: int = 0, negate_z: bool = False, cameras=None) -> dict:
     """The correspondences of a first-pose fit from a frame's images (include/captra_hip.h: captra_image_members, where the rule is
     stated): the pixels of the instance mask, eroded by `border`, that carry a depth, in row-major order, at most `cap` of them (a
     fixed stride thins a larger instance), back-projected and paired with the NOCS coordinates the coordinate image encodes.
@@ -320,7 +400,10 @@ def image_members(depth: torch.Tensor, mask: torch.Tensor, coord: torch.Tensor, 
     and contiguous; (H,W) / (H,W,3) for one image.
     -> {'src' (B,1,3,cap) fp32, 'tgt' (B,3,cap) fp32 metres, 'labels' (B,cap) int32 (0 = a member, -1 = an empty slot), 'pix' (B,cap)
     int32, 'counts' (B,3) int32 = members, used, holes}: what part_fit_ransac_cn(labels, src, tgt) reads.  One launch, nothing
-    visits the host."""
+    visits the host.
+    `cameras` = (table (C,19) float64, cam_of (B,) int32) device tensors (camera_table): image i is back-projected with the K^-1 and
+    the depth unit of camera cam_of[i] (captra_image_members_cam), `intrinsics` is not read and the depth is in that camera's counts.
+    None: the call as it always was."""
     from . import _lib as L
     L.require_device(depth, mask, coord)
     single = depth.dim() == 2
@@ -337,20 +420,28 @@ def image_members(depth: torch.Tensor, mask: torch.Tensor, coord: torch.Tensor, 
     cap, border = check_image_fit_params(cap, border)
     B, H, W = depth.shape
     dev = depth.device
-    kinv = _intrinsics_on_device(intrinsics, dev)[9:]
+    if cameras is not None:
+        cam_table, cam_of = _check_cameras(cameras, B, dev)
+    else:
+        kinv = _intrinsics_on_device(intrinsics, dev)[9:]
     out = {"src": torch.empty(B, 1, 3, cap, dtype=torch.float32, device=dev), "tgt": torch.empty(B, 3, cap, dtype=torch.float32, device=dev),
            "labels": torch.empty(B, cap, dtype=torch.int32, device=dev), "pix": torch.empty(B, cap, dtype=torch.int32, device=dev),
            "counts": torch.zeros(B, 3, dtype=torch.int32, device=dev)}
     with torch.cuda.device(dev):
-        L.call("captra_image_members", B, H, W, cap, border, 1 if negate_z else 0, L.ptr(depth), L.ptr(mask.view(torch.uint8)), L.ptr(coord),
-               L.ptr(kinv), L.ptr(out["src"]), L.ptr(out["tgt"]), L.ptr(out["labels"]), L.ptr(out["pix"]), L.ptr(out["counts"]))
+        if cameras is not None:
+            L.call("captra_image_members_cam", B, H, W, cap, border, 1 if negate_z else 0, L.ptr(depth), L.ptr(mask.view(torch.uint8)), L.ptr(coord),
+                   cam_table.shape[0], L.ptr(cam_table), L.ptr(cam_of), L.ptr(out["src"]), L.ptr(out["tgt"]), L.ptr(out["labels"]), L.ptr(out["pix"]),
+                   L.ptr(out["counts"]))
+        else:
+            L.call("captra_image_members", B, H, W, cap, border, 1 if negate_z else 0, L.ptr(depth), L.ptr(mask.view(torch.uint8)), L.ptr(coord),
+                   L.ptr(kinv), L.ptr(out["src"]), L.ptr(out["tgt"]), L.ptr(out["labels"]), L.ptr(out["pix"]), L.ptr(out["counts"]))
     if H * W == 0:                      # images without a pixel: the call has nothing to do and writes nothing
         out["src"].zero_(); out["tgt"].zero_(); out["labels"].fill_(-1); out["pix"].fill_(-1)
     return {k: v[0] for k, v in out.items()} if single else out
 
 
 def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, intrinsics=NOCS_REAL_INTRINSICS, stacked: bool = True,
-                           pose_dev=None, gt_dev=None, defer=None, mean=None, det=None, thin=None):
+                           pose_dev=None, gt_dev=None, defer=None, mean=None, det=None, thin=None, cameras=None):
     """full_data_batch on already-stacked inputs (the track loop's form: no per-trajectory Python on the frame's critical
     path): depth (B,H,W), mask (B,H,W) device tensors; centers (B,3), radii_in (B,) float64 host arrays (radius as handed to
     full_data_from_depth: clamped to 0.05 inside); gt = {'rotation' (B,3,3), 'translation' (B,3), 'scale' (B,)} float64 host arrays.
@@ -372,7 +463,11 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
     launch sits between the crop and the candidate launch and such an instance is no rare-path instance; on the synchronous stage the
     same launch fills the row's table and nothing is drawn from numpy for it, so both stages produce the same clouds bit for bit.
     Instances on the torch path (fewer than 10 members or more than CROP_CAP: crop_candidates) keep the host's permutation.  The
-    stacked results then carry '_thinned' (B,) int32: which instances were thinned."""
+    stacked results then carry '_thinned' (B,) int32: which instances were thinned.
+    `cameras` = (table (C,19) float64, cam_of (B,) int32) device tensors (camera_table): the camera model -- trajectory i is projected
+    and back-projected with camera cam_of[i]'s K, K^-1 and depth unit in every branch (the *_cam entry points, include/captra_hip.h;
+    the host-box branch projects each row with its own K; a rare-path instance's torch path takes its K and unit), `intrinsics` is
+    not read and the depth images are in their cameras' counts.  None: the calls as they always were, bit for bit."""
     from . import _lib as L, fused
     dev = depth.device
     if thin is not None and dev.type != "cuda":
@@ -381,6 +476,21 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
     depth = depth.to(torch.int32).contiguous()
     mask = mask.to(torch.uint8).contiguous()
     _, H, W = depth.shape
+    cam_table = cam_of = cams_h = None
+    if cameras is not None:
+        if dev.type != "cuda":
+            raise ValueError("the camera model of the re-crop (cameras=(table, cam_of)) runs on the device: it needs the frames there")
+        cam_table, cam_of = _check_cameras(cameras, B, dev)
+        ncam = int(cam_table.shape[0])
+
+    def cameras_on_host():
+        """(K (B,3,3), depth_unit (B,)) of the rows, fetched once: the host-box branch and the rare path's torch restatement."""
+        nonlocal cams_h
+        if cams_h is None:
+            t = to_host(cam_table)[np.clip(to_host(cam_of), 0, ncam - 1)]
+            cams_h = (t[:, :9].reshape(B, 3, 3).copy(), t[:, 18].copy())
+        return cams_h
+
     if det is not None:
         if pose_dev is None or dev.type != "cuda":
             raise ValueError("the detector route of the re-crop selects its masks on the device: it takes the pose as `pose_dev`")
@@ -409,6 +519,18 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
             if det is not None:
                 raw_d = torch.empty(B, dtype=torch.float64, device=dev)
                 sel_d = torch.empty(B, dtype=torch.int32, device=dev)
+            if cameras is not None and det is not None:
+                L.call("captra_crop_box_det_cam", B, H, W, K, int(det["category"]), float(factor), L.ptr(trans_d), L.ptr(scale_d), ncam, L.ptr(cam_table),
+                       L.ptr(cam_of), L.ptr(det_boxes), L.ptr(det_class), L.ptr(det_count), L.ptr(box_d), L.ptr(ctr_d), L.ptr(rad_d), L.ptr(raw_d),
+                       L.ptr(sel_d))
+                L.call("captra_crop_ball_det_cam", B, H, W, CROP_CAP, K, L.ptr(depth), L.ptr(mask), L.ptr(det_masks), L.ptr(sel_d), L.ptr(box_d),
+                       L.ptr(ctr_d), L.ptr(rad_d), ncam, L.ptr(cam_table), L.ptr(cam_of), L.ptr(pts), L.ptr(obj), L.ptr(pix), L.ptr(counts))
+            elif cameras is not None:
+                L.call("captra_crop_box_cam", B, H, W, float(factor), L.ptr(trans_d), L.ptr(scale_d), ncam, L.ptr(cam_table), L.ptr(cam_of),
+                       L.ptr(box_d), L.ptr(ctr_d), L.ptr(rad_d))
+                L.call("captra_crop_ball_cam", B, H, W, CROP_CAP, L.ptr(depth), L.ptr(mask), L.ptr(box_d), L.ptr(ctr_d), L.ptr(rad_d), ncam,
+                       L.ptr(cam_table), L.ptr(cam_of), L.ptr(pts), L.ptr(obj), L.ptr(pix), L.ptr(counts))
+            elif det is not None:
                 L.call("captra_crop_box_det", B, H, W, K, int(det["category"]), float(factor), L.ptr(trans_d), L.ptr(scale_d), kk.data_ptr(),
                        L.ptr(det_boxes), L.ptr(det_class), L.ptr(det_count), L.ptr(box_d), L.ptr(ctr_d), L.ptr(rad_d), L.ptr(raw_d), L.ptr(sel_d))
                 L.call("captra_crop_ball_det", B, H, W, CROP_CAP, K, L.ptr(depth), L.ptr(mask), L.ptr(det_masks), L.ptr(sel_d), L.ptr(box_d),
@@ -421,7 +543,11 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
         centers = np.ascontiguousarray(np.asarray(centers, np.float64).reshape(B, 3))
         radii_in = np.asarray(radii_in, np.float64).reshape(B)
         radii = np.maximum(radii_in, 0.05)
-        boxes = proj_corners_batch(H, W, centers, radii_in, intrinsics).reshape(B, 4).astype(np.int32)
+        if cameras is not None:        # each row projected with its own K (the same float64 operations, one row at a time)
+            boxes = np.stack([proj_corners_batch(H, W, centers[b:b + 1], radii_in[b:b + 1], cameras_on_host()[0][b]).reshape(4)
+                              for b in range(B)]).astype(np.int32)
+        else:
+            boxes = proj_corners_batch(H, W, centers, radii_in, intrinsics).reshape(B, 4).astype(np.int32)
         kinv = _kinv(intrinsics)
         # ONE host-to-device copy for everything the crop kernel reads from the host: the doubles (centres, radii, K^-1), then
         # the int32 boxes (this stretch of host work sits between the pose round trip and the crop launch: the GPU waits for it)
@@ -432,8 +558,12 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
         host = to_device(blob, dev)
         hp = host.data_ptr()
         with torch.cuda.device(dev):
-            L.call("captra_crop_ball", B, H, W, CROP_CAP, L.ptr(depth), L.ptr(mask), hp + 8 * ndbl, hp,
-                   hp + 8 * 3 * B, hp + 8 * 4 * B, L.ptr(pts), L.ptr(obj), L.ptr(pix), L.ptr(counts))
+            if cameras is not None:
+                L.call("captra_crop_ball_cam", B, H, W, CROP_CAP, L.ptr(depth), L.ptr(mask), hp + 8 * ndbl, hp, hp + 8 * 3 * B, ncam,
+                       L.ptr(cam_table), L.ptr(cam_of), L.ptr(pts), L.ptr(obj), L.ptr(pix), L.ptr(counts))
+            else:
+                L.call("captra_crop_ball", B, H, W, CROP_CAP, L.ptr(depth), L.ptr(mask), hp + 8 * ndbl, hp,
+                       hp + 8 * 3 * B, hp + 8 * 4 * B, L.ptr(pts), L.ptr(obj), L.ptr(pix), L.ptr(counts))
     table_t = thinned_t = None
     if thin is not None:
         # the thinning launch (a workgroup per instance, which leaves at once when its list is not over-long): behind the crop in BOTH
@@ -504,7 +634,11 @@ def full_data_batch_arrays(depth, mask, centers, radii_in, gt, num_points: int, 
         c = int(n_members[b])
         if c < 10 or c > CROP_CAP:
             mask_b = det_masks[b, int(sel_h[b])] if sel_h is not None and sel_h[b] >= 0 else mask[b]
-            slow[b] = crop_candidates(depth[b], mask_b.bool(), centers[b], float(radii_in[b]), num_points, intrinsics)
+            if cameras is not None:
+                slow[b] = crop_candidates(depth[b], mask_b.bool(), centers[b], float(radii_in[b]), num_points, cameras_on_host()[0][b],
+                                          depth_unit=float(cameras_on_host()[1][b]))
+            else:
+                slow[b] = crop_candidates(depth[b], mask_b.bool(), centers[b], float(radii_in[b]), num_points, intrinsics)
             continue
         length = c
         while length < num_points:

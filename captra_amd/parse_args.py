@@ -43,9 +43,14 @@ _FLAGS = [  # (name, type, default)
     # the re-crop's over-long candidate lists thinned on the device (track_options.py: otf_thin_cfg); off unless device is True
     ("track_cfg/otf_thin/device", boolean_string, None), ("track_cfg/otf_thin/seed", int, None),
     # flying depth pixels removed from every uploaded depth image (track_options.py: depth_filter_cfg); on when any of the four is
-    # given, and then abs_mm (millimetres) and min_support are required
+    # given, and then abs_mm (depth counts: millimetres for a millimetre sensor) and min_support are required
     ("track_cfg/depth_filter/window", int, None), ("track_cfg/depth_filter/abs_mm", int, None),
     ("track_cfg/depth_filter/rel_permille", int, None), ("track_cfg/depth_filter/min_support", int, None),
+    # the camera of the depth images (track_options.py: camera_cfg): a preset, or fx / fy / cx / cy (required then), skew and depth_unit
+    # (metres per depth count).  Not given = not in the namespace at all, like yaxis_only: no `camera` section appears
+    ("camera/preset", str, argparse.SUPPRESS), ("camera/fx", float, argparse.SUPPRESS), ("camera/fy", float, argparse.SUPPRESS),
+    ("camera/cx", float, argparse.SUPPRESS), ("camera/cy", float, argparse.SUPPRESS), ("camera/skew", float, argparse.SUPPRESS),
+    ("camera/depth_unit", float, argparse.SUPPRESS),
     # every step starts from a constant-velocity prediction (track_options.py: motion_cfg); off unless predict is True, and then max_angle
     # (degrees) and max_shift (a fraction of data_radius) are required
     ("track_cfg/motion/predict", boolean_string, None), ("track_cfg/motion/max_angle", float, None),

@@ -172,7 +172,7 @@ FLYING_STREAM = 0xF1E1          # make_frame's flying pixels: the first word of 
 
 
 def make_frame(seed: int, height: int = 480, width: int = 640, dr: float = 0.0, dc: float = 0.0, blob_px: float = 70, flying: float = 0.0,
-               return_flying: bool = False):
+               return_flying: bool = False, intrinsics=None, depth_scale=1):
     """Synthetic depth frame (uint16 mm) with an object blob in front of a wavy background, its mask, a predicted centre
     and radius, and an instance pose.  (dr, dc): the blob displaced by that many pixel rows / columns -- a moving object over
     the frames of a trajectory; the defaults are golden G11's frames.  blob_px: the blob's radius in pixels (70: about 15 100 ball
@@ -182,7 +182,12 @@ def make_frame(seed: int, height: int = 480, width: int = 640, dr: float = 0.0, 
     the blob (900..940 at blob_px 70, up to 953 at its rim at blob_px 90) and the background (about 1360..1640) and more than 20 mm
     from either, so that no genuine pixel supports a flying one at a tolerance of up to 20 mm.  Drawn from a generator of its own,
     seeded from `seed`: the frame's own stream does not move, and flying = 0.0 is the frame as it always was.  return_flying: the
-    mask of the injected pixels as a fifth result."""
+    mask of the injected pixels as a fifth result.
+    intrinsics (3,3): the camera that watches the frame -- the SAME pixels seen through another K: the centre and the pose are the
+    blob's pixel back-projected with it at the same depth, so the re-crop under that camera finds the blob where this frame puts it.
+    depth_scale: the sensor counts depth_scale counts per millimetre (2: half millimetres, depth_unit 0.0005) -- every count of the
+    uint16 image multiplied AFTER its rounding to whole millimetres, so the frame holds the same 3D surface exactly; it must keep the
+    counts inside uint16.  The defaults (None: the NOCS REAL matrix; 1) are the frame as it always was, byte for byte."""
     rng = np.random.default_rng(seed)
     r, c = np.mgrid[0:height, 0:width]
     depth = 1500.0 + 80.0 * np.sin(r / 37.0) + 60.0 * np.cos(c / 53.0)
@@ -198,7 +203,12 @@ def make_frame(seed: int, height: int = 480, width: int = 640, dr: float = 0.0, 
         injected = (np.abs(rr - blob_px) <= 1.5) & (depth > 0) & (fly_rng.random(depth.shape) < flying)
         depth[injected] = fly_rng.integers(975, 1131, size=depth.shape)[injected].astype(np.uint16)
     mask = blob & (rng.random(depth.shape) < 0.97)
-    K = np.array([[591.0125, 0, 322.525], [0, 590.16775, 244.11084], [0, 0, 1]])
+    if depth_scale != 1:
+        scaled = np.round(depth.astype(np.float64) * float(depth_scale))
+        if scaled.max() > np.iinfo(np.uint16).max:
+            raise ValueError(f"depth_scale {depth_scale} takes the frame's counts beyond uint16")
+        depth = scaled.astype(np.uint16)
+    K = np.array([[591.0125, 0, 322.525], [0, 590.16775, 244.11084], [0, 0, 1]]) if intrinsics is None else np.asarray(intrinsics, np.float64)
     z = 0.95
     center = np.array([(cc - K[0, 2]) / K[0, 0] * z, ((height - cr) - K[1, 2]) / K[1, 1] * z, -z]) + 0.01 * rng.standard_normal(3)
     th = 0.4
@@ -350,18 +360,19 @@ def make_physical_state_dict(shapes: dict, seed: int, num_parts: int, sym: bool,
     return sd
 
 
-def render_coord_image(depth, mask, pose, intrinsics=None) -> np.ndarray:
+def render_coord_image(depth, mask, pose, intrinsics=None, depth_unit=None) -> np.ndarray:
     """The NOCS coordinate image (h,w,3) uint8 of an instance, as a NOCS-style detector or the NOCS dataset delivers it (channel k =
     NOCS axis k), rendered from the frame's own depth (h,w) and ground-truth pose {'rotation' (3,3), 'translation' (3,1), 'scale'}:
     every pixel back-projected as the re-crop does (ray = K^-1 (col, h - row, 1); p = ray * z / ray_z; (p_x, p_y, -p_z) * 0.001), NOCS
-    = R^T (p - t) / s, encoded as round((nocs + 0.5) * 255) clipped to [0, 255]; zero off the mask."""
+    = R^T (p - t) / s, encoded as round((nocs + 0.5) * 255) clipped to [0, 255]; zero off the mask.  depth_unit: metres per depth count
+    (None: the 0.001 of a millimetre image)."""
     K = np.array([[591.0125, 0, 322.525], [0, 590.16775, 244.11084], [0, 0, 1]]) if intrinsics is None else np.asarray(intrinsics, np.float64)
     h, w = depth.shape
     r, c = np.mgrid[0:h, 0:w]
     ray = np.stack([c, h - r, np.ones_like(r)], -1).astype(np.float64) @ np.linalg.inv(K).T
     p = ray * depth.astype(np.float32).astype(np.float64)[..., None] / ray[..., 2:3]
     p[..., 2] = -p[..., 2]
-    p *= 0.001
+    p *= 0.001 if depth_unit is None else float(depth_unit)
     R, t, s = np.asarray(pose["rotation"], np.float64), np.asarray(pose["translation"], np.float64).reshape(3), float(pose["scale"])
     nocs = (p - t) @ R / s
     img = np.clip(np.round((nocs + 0.5) * 255.0), 0, 255).astype(np.uint8)
@@ -370,7 +381,7 @@ def render_coord_image(depth, mask, pose, intrinsics=None) -> np.ndarray:
 
 
 def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float = 6.0, blob_px: float = 70, flying: float = 0.0,
-                        coord: bool = False):
+                        coord: bool = False, cameras=None):
     """A trajectory for the on-the-fly re-crop loop (`nocs_otf=True`, reference model.py:425-452): the frame dicts of
     make_trajectory('nocs', ...) carrying, per frame, the depth image / instance mask the loop re-crops
     (meta['pre_fetched']) and the blob's ground-truth pose (meta['nocs2camera']); trajectory b watches depth frame
@@ -379,16 +390,30 @@ def make_otf_trajectory(batch: int, frames: int, seed: int = 0, step_px: float =
     candidate lists are thinned).  flying: make_frame's (> 0: flying pixels along the silhouette, their mask (B,H,W) bool in
     meta['pre_fetched']['flying']).  coord: frame 0 also carries meta['pre_fetched']['coord'] (B,h,w,3) uint8, the NOCS coordinate image
     of the blob rendered from the frame's own depth and ground-truth pose (render_coord_image) -- what `init_frame/image_fit` reads;
-    False: exactly the frames as they always were."""
+    False: exactly the frames as they always were.
+    cameras: a per-trajectory list of (K (3,3) or None = NOCS REAL, depth_unit, depth_scale): trajectory b's frames are make_frame's for
+    that camera (intrinsics = K, depth_scale) -- the same 3D blob in that camera's pixels and counts --, and every frame carries
+    meta['pre_fetched']['camera'] = {'K' (B,3,3), 'depth_unit' (B,)} float64.  None: no camera anywhere, today's bytes."""
     data = make_trajectory("nocs", batch, frames, seed=seed)
+    if cameras is not None and len(cameras) != batch:
+        raise ValueError(f"cameras: one (K, depth_unit, depth_scale) per trajectory, got {len(cameras)} for {batch}")
+    real = np.array([[591.0125, 0, 322.525], [0, 590.16775, 244.11084], [0, 0, 1]])
+    cam_kw = [{} if cameras is None else {"intrinsics": cameras[b][0], "depth_scale": cameras[b][2]} for b in range(batch)]
     for t, f in enumerate(data):
-        views = [make_frame(seed + b, dr=0.5 * step_px * t, dc=step_px * t, blob_px=blob_px, flying=flying, return_flying=True) for b in range(batch)]
+        views = [make_frame(seed + b, dr=0.5 * step_px * t, dc=step_px * t, blob_px=blob_px, flying=flying, return_flying=True, **cam_kw[b])
+                 for b in range(batch)]
         f["meta"]["pre_fetched"] = {"depth": torch.from_numpy(np.stack([v[0].astype(np.int32) for v in views])),
                                     "mask": torch.from_numpy(np.stack([v[1] for v in views]))}
         if flying > 0.0:
             f["meta"]["pre_fetched"]["flying"] = torch.from_numpy(np.stack([v[4] for v in views]))
         if coord and t == 0:
-            f["meta"]["pre_fetched"]["coord"] = torch.from_numpy(np.stack([render_coord_image(v[0], v[1], v[3]) for v in views]))
+            f["meta"]["pre_fetched"]["coord"] = torch.from_numpy(np.stack([
+                render_coord_image(v[0], v[1], v[3], *(() if cameras is None else (real if cameras[b][0] is None else cameras[b][0], cameras[b][1])))
+                for b, v in enumerate(views)]))
+        if cameras is not None:
+            f["meta"]["pre_fetched"]["camera"] = {
+                "K": torch.from_numpy(np.stack([real if c[0] is None else np.asarray(c[0], np.float64) for c in cameras])),
+                "depth_unit": torch.tensor([float(c[1]) for c in cameras], dtype=torch.float64)}
         f["meta"]["path"] = [f"synthetic/1/inst{seed + b}/track0/{t:04d}.npz" for b in range(batch)]
         f["meta"]["ori_path"] = [f"synthetic/scene_{seed + b}/{t:04d}_depth.png" for b in range(batch)]
         for p in f["meta"]["nocs2camera"]:
@@ -409,6 +434,8 @@ def cat_trajectories(parts):
                 "pre_fetched": {k: torch.cat([f["meta"]["pre_fetched"][k] for f in frames]) for k in ("depth", "mask")},
                 "nocs2camera": [{k: torch.cat([f["meta"]["nocs2camera"][p][k] for f in frames]) for k in ("rotation", "translation", "scale")}
                                 for p in range(len(f0["meta"]["nocs2camera"]))]}
+        if all("camera" in f["meta"]["pre_fetched"] for f in frames):      # (make_otf_trajectory(..., cameras=...): the trajectories' cameras)
+            meta["pre_fetched"]["camera"] = {k: torch.cat([f["meta"]["pre_fetched"]["camera"][k] for f in frames]) for k in ("K", "depth_unit")}
         out.append({"points": torch.cat([f["points"] for f in frames]), "labels": torch.cat([f["labels"] for f in frames]),
                     "nocs": torch.cat([f["nocs"] for f in frames]), "meta": meta})
     return out

@@ -188,7 +188,7 @@ def _load_source(src, args, cfg=None):
             data = clouds.make_otf_trajectory(1, args.num_frames, seed=seed, coord=bool(cfg["init_frame"].get("image_fit", False)))
             return clouds.make_otf_detections(1, args.num_frames, seed=seed, data=data) if det else data
         return clouds.make_trajectory(kind, 1, args.num_frames, seed=seed)
-    frames = stack_trajectories([load_trajectory_npz(src)])
+    frames = stack_trajectories([load_trajectory_npz(src)])          # (its camera, when the file has one, rides in meta['pre_fetched'])
     if det and cfg["track_cfg"].get("nocs2d_path") and "pre_fetched" in frames[0]["meta"] and "det_boxes" not in frames[0]["meta"]["pre_fetched"]:
         from .trajectory_io import attach_nocs2d_detections
         attach_nocs2d_detections(frames, cfg["track_cfg"]["nocs2d_path"])
@@ -199,6 +199,7 @@ def iter_batches(args, cfg, ranks: Ranks | None = None):
     """Yields lists over frames of batched frame dicts, at most cfg['batch_size'] trajectories of THIS rank's shard at a
     time (equal frame counts and cloud sizes batch together)."""
     from .parallel import shard_range
+    from .track_options import camera_cfg
     from .trajectory_io import concat_frame_batches
     B = max(int(cfg.get("batch_size") or 1), 1)
     sources = _trajectory_sources(args, cfg)
@@ -213,7 +214,7 @@ def iter_batches(args, cfg, ranks: Ranks | None = None):
         shape = (len(trajs[i]), tuple(trajs[i][0]["points"].shape[1:]))
         while j < len(trajs) and j - i < B and (len(trajs[j]), tuple(trajs[j][0]["points"].shape[1:])) == shape:
             j += 1
-        yield concat_frame_batches(trajs[i:j])
+        yield concat_frame_batches(trajs[i:j], default_camera=camera_cfg(cfg))
         i = j
 
 

@@ -139,7 +139,8 @@ def depth_filter_cfg(cfg):
     frame over all trajectories, outside the step, the lanes and the replay of a flagged frame, which all read the filtered
     image.  The removed pixels are recorded per frame and trajectory (pred_dict / pickle 'depth_filter').  None when absent (the
     upload is used as it is), else the four inside the kernel's ranges; abs_mm and min_support have no default: the right values
-    depend on the sensor and on the window."""
+    depend on the sensor and on the window.  abs_mm is in DEPTH COUNTS -- millimetres for a millimetre sensor, hence the name; under
+    a `camera` whose depth_unit is not 0.001 it is abs_mm x depth_unit metres (the kernel compares counts and knows no unit)."""
     from .nocs_otf import check_depth_filter_params
     f = cfg["track_cfg"].get("depth_filter")
     if f is None:
@@ -154,6 +155,73 @@ def depth_filter_cfg(cfg):
     vals = check_depth_filter_params(2 if window is None else window, f["abs_mm"], 0 if rel is None else rel, f["min_support"],
                                      prefix="track_cfg/depth_filter/")
     return dict(zip(("window", "abs_mm", "rel_permille", "min_support"), vals))
+
+
+CAMERA_KEYS = ("fx", "fy", "cx", "cy", "skew", "depth_unit")
+
+
+def camera_cfg(cfg):
+    """camera: {preset: nocs_real | nocs_camera} or camera: {fx, fy, cx, cy, skew: 0, depth_unit: 0.001}: the camera of every trajectory
+    that does not carry its own (meta['pre_fetched']['camera']) -- the intrinsics the re-crop projects and back-projects with and the
+    depth unit, metres per depth count (csrc/crop.hip, csrc/image_fit.hip: the *_cam entry points, include/captra_hip.h).  The pixel
+    and frame convention stays the reference's: ray = K^-1 (col, h - row, 1), p_z negated.  nocs_real is the camera everything was wired
+    to (591.0125, 590.16775, 322.525, 244.11084); nocs_camera the CAMERA25 images' (577.5, 577.5, 319.5, 239.5); both count millimetres.
+    None when absent (the plain entry points are called and no camera tensor exists), else {'K' (3,3) float64, 'depth_unit' float}; a
+    camera that is not valid is a ValueError that names the key."""
+    from .nocs_otf import CAMERA_PRESETS, check_camera
+    c = cfg.get("camera")
+    if c is None:
+        return None
+    if not isinstance(c, dict):
+        raise ValueError(f"camera must be a section (preset, or fx / fy / cx / cy / skew / depth_unit), got {c!r}")
+    unknown = [k for k in c if k != "preset" and k not in CAMERA_KEYS]
+    if unknown:
+        raise ValueError(f"camera: unknown keys {unknown} (preset, or {', '.join(CAMERA_KEYS)})")
+    if not cfg.get("nocs_otf", False) and not cfg["init_frame"].get("image_fit", False):
+        raise ValueError("camera is the camera of the depth images the on-the-fly re-crop and the first-pose image fit read: it needs "
+                         "nocs_otf: True or init_frame/image_fit: True (without them there is no depth image)")
+    given = [k for k in CAMERA_KEYS if c.get(k) is not None]
+    if c.get("preset") is not None:
+        if given:
+            raise ValueError(f"camera/preset and camera/{given[0]} both describe the camera: set the preset or the explicit keys")
+        if c["preset"] not in CAMERA_PRESETS:
+            raise ValueError(f"camera/preset must be one of {sorted(CAMERA_PRESETS)}, got {c['preset']!r}")
+        K, unit = CAMERA_PRESETS[c["preset"]]
+    else:
+        vals = {}
+        for key, default in (("fx", None), ("fy", None), ("cx", None), ("cy", None), ("skew", 0.0), ("depth_unit", 0.001)):
+            v = c.get(key)
+            v = default if v is None else v
+            if v is None:
+                raise ValueError(f"camera needs camera/{key}: it has no default (or set camera/preset)")
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"camera/{key} must be a number, got {v!r}")
+            vals[key] = float(v)
+        K = np.array([[vals["fx"], vals["skew"], vals["cx"]], [0.0, vals["fy"], vals["cy"]], [0.0, 0.0, 1.0]])
+        unit = vals["depth_unit"]
+    K, unit = check_camera(K, unit, prefix="camera/")
+    return {"K": K.copy(), "depth_unit": unit}
+
+
+def trajectory_cameras(frame_camera, cfg_camera, batch: int):
+    """The cameras of a batch's trajectories, by precedence: frame 0's own (meta['pre_fetched']['camera'] = {'K' (B,3,3), 'depth_unit'
+    (B,)}), then the configuration's (camera_cfg) for all of them, then None.  -> None or {'K' (B,3,3), 'depth_unit' (B,)} float64 host
+    arrays, each camera checked (a ValueError names the entry)."""
+    from .nocs_otf import check_camera
+    if frame_camera is not None:
+        missing = [k for k in ("K", "depth_unit") if k not in frame_camera]
+        if missing:
+            raise ValueError(f"meta['pre_fetched']['camera'] needs {missing}: it is {{'K': (B,3,3), 'depth_unit': (B,)}}")
+        to_np = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float64)
+        K, unit = to_np(frame_camera["K"]), to_np(frame_camera["depth_unit"]).reshape(-1)
+        if K.shape != (batch, 3, 3) or unit.shape != (batch,):
+            raise ValueError(f"meta['pre_fetched']['camera']: K (B,3,3) and depth_unit (B,) with B = {batch} trajectories, got {K.shape} and {unit.shape}")
+        for b in range(batch):
+            check_camera(K[b], unit[b], prefix=f"meta['pre_fetched']['camera'] of trajectory {b}: ")
+        return {"K": K.copy(), "depth_unit": unit.copy()}
+    if cfg_camera is not None:
+        return {"K": np.broadcast_to(cfg_camera["K"], (batch, 3, 3)).copy(), "depth_unit": np.full(batch, cfg_camera["depth_unit"], np.float64)}
+    return None
 
 
 def motion_cfg(cfg):
@@ -276,7 +344,8 @@ STEP_RECORDS = {"guard": ("guard_", ("count", "inliers", "rms", "verdict")),    
 # The host loop's records, ONE (B,) int32 tensor per frame (None: a frame without) -> the key that wraps it in the pickle.
 # otf_thin: which trajectories' lists were thinned (its sum: the frame's thinned instances); depth_filter: the pixels set to 0
 LOOP_RECORDS = {"otf_thin": "thinned", "depth_filter": "removed"}
-# (and frame 0's one-off "image_fit": a flat dict of (B,) int32 tensors -- members, used, holes, inliers, valid)
+# (and frame 0's one-off "image_fit": a flat dict of (B,) int32 tensors -- members, used, holes, inliers, valid;
+#  and the trajectories' "camera": {'K' (B,3,3), 'depth_unit' (B,)} float64, present when a camera is in use)
 
 
 def put_record(npcs_pred, name, values):
@@ -311,4 +380,6 @@ def records_to_numpy(pred_dict, guard_yaxis_only=False):
     out.update({name: [None if r is None else {key: to_np(r)} for r in pred_dict[name]] for name, key in LOOP_RECORDS.items() if name in pred_dict})
     if "image_fit" in pred_dict:
         out["image_fit"] = {k: to_np(v) for k, v in pred_dict["image_fit"].items()}
+    if "camera" in pred_dict:           # (host arrays already: K (B,3,3), depth_unit (B,))
+        out["camera"] = {k: np.asarray(v, np.float64) for k, v in pred_dict["camera"].items()}
     return out

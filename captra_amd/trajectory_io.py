@@ -18,9 +18,13 @@ per trajectory -- the arrays a dataset item holds after cropping to N points:
                                the frames' 2D detections for `--track_cfg/nocs2d_label True`, K slots of which the first det_count hold one
     coord        (H,W,3) uint8 optional (with depth / mask): FRAME 0's NOCS coordinate image, channel k = NOCS axis k, for
                                `--init_frame/image_fit True` (the first pose fitted from images alone)
+    camera_K (3,3) f64, camera_depth_unit () f64, optional (with depth / mask): the trajectory's camera -- intrinsics and metres per
+                               depth count (the `camera` option, track_options.py); a trajectory without them is seen through the
+                               configuration's camera, or the NOCS REAL one
     ori_paths    (T,) str      optional: "…/<scene>/<frame>_depth.png" (meta['ori_path']): names the detector result file of a frame
 
-`stack_trajectories` batches B trajectories of equal length into the (B, …) frame dicts `set_data` takes.
+`stack_trajectories` batches B trajectories of equal length into the (B, …) frame dicts `set_data` takes.  The images of one batch
+share their size H x W: a batch with several image sizes is a ValueError.
 """
 from __future__ import annotations
 
@@ -30,6 +34,23 @@ import torch
 _KEYS = ("points", "points_mean", "labels", "nocs", "rotation", "translation", "scale", "nocs_corners", "paths")
 DET_KEYS = ("det_boxes", "det_class", "det_count", "det_masks")
 _DET_DTYPES = {"det_boxes": np.int32, "det_class": np.int32, "det_count": np.int32, "det_masks": np.uint8}
+CAMERA_KEYS = ("camera_K", "camera_depth_unit")
+
+
+def _default_camera(default_camera) -> tuple:
+    """(K (3,3), depth_unit) a trajectory without a camera of its own gets in a mixed batch: the configuration's ({'K', 'depth_unit'},
+    track_options.camera_cfg) or the NOCS REAL camera, which is what such a trajectory was always seen through."""
+    from .nocs_otf import CAMERA_PRESETS
+    if default_camera is None:
+        K, unit = CAMERA_PRESETS["nocs_real"]
+        return np.asarray(K, np.float64), float(unit)
+    return np.asarray(default_camera["K"], np.float64).reshape(3, 3), float(default_camera["depth_unit"])
+
+
+def _one_image_size(shapes, what: str) -> None:
+    sizes = sorted({tuple(int(x) for x in s[-2:]) for s in shapes})
+    if len(sizes) > 1:
+        raise ValueError(f"{what}: the images of one batch share their size H x W, got {sizes} (batch the trajectories by image size)")
 
 
 def save_trajectory_npz(path: str, frames: list, b: int = 0) -> None:
@@ -54,6 +75,10 @@ def save_trajectory_npz(path: str, frames: list, b: int = 0) -> None:
                 out[k] = np.stack([np.asarray(f["meta"]["pre_fetched"][k][b]) for f in frames]).astype(_DET_DTYPES[k])
         if "coord" in frames[0]["meta"]["pre_fetched"]:
             out["coord"] = np.asarray(frames[0]["meta"]["pre_fetched"]["coord"][b]).astype(np.uint8)
+        if "camera" in frames[0]["meta"]["pre_fetched"]:
+            cam = frames[0]["meta"]["pre_fetched"]["camera"]
+            out["camera_K"] = np.asarray(cam["K"][b], np.float64).reshape(3, 3)
+            out["camera_depth_unit"] = np.float64(np.asarray(cam["depth_unit"][b], np.float64).reshape(()))
     if all("ori_path" in f["meta"] for f in frames):
         out["ori_paths"] = np.array([f["meta"]["ori_path"][b] for f in frames])
     np.savez(path, **out)
@@ -65,17 +90,24 @@ def load_trajectory_npz(path: str) -> dict:
         if missing:
             raise ValueError(f"{path}: not a trajectory file, missing {missing}")
         traj = {k: z[k] for k in _KEYS}
-        for k in ("depth", "mask", "coord", "ori_paths") + DET_KEYS:
+        for k in ("depth", "mask", "coord", "ori_paths") + DET_KEYS + CAMERA_KEYS:
             if k in z.files:
                 traj[k] = z[k]
     T = traj["points"].shape[0]
     if not all(traj[k].shape[0] == T for k in ("points_mean", "labels", "nocs", "rotation", "translation", "scale", "paths")):
         raise ValueError(f"{path}: inconsistent frame counts")
+    if any(k in traj for k in CAMERA_KEYS):
+        if not all(k in traj for k in CAMERA_KEYS) or "depth" not in traj:
+            raise ValueError(f"{path}: a trajectory's camera is camera_K (3,3) AND camera_depth_unit, beside its depth images")
+        from .nocs_otf import check_camera
+        check_camera(traj["camera_K"], traj["camera_depth_unit"], prefix=f"{path}: camera_")
     return traj
 
 
-def stack_trajectories(trajs: list) -> list:
-    """B trajectory dicts of equal length T -> list over T of batched frame dicts (CPU tensors)."""
+def stack_trajectories(trajs: list, default_camera=None) -> list:
+    """B trajectory dicts of equal length T -> list over T of batched frame dicts (CPU tensors).  When a trajectory carries its camera
+    (camera_K, camera_depth_unit) every frame gets meta['pre_fetched']['camera'] = {'K' (B,3,3), 'depth_unit' (B,)}; in such a MIXED stack a
+    trajectory without one gets `default_camera` ({'K', 'depth_unit'}: the configuration's) or the NOCS REAL camera."""
     T = trajs[0]["points"].shape[0]
     if any(t["points"].shape != trajs[0]["points"].shape for t in trajs):
         raise ValueError("trajectories of one batch must share the frame count and the number of points")
@@ -89,23 +121,30 @@ def stack_trajectories(trajs: list) -> list:
         meta = {"path": [str(t["paths"][i]) for t in trajs], "nocs2camera": poses, "points_mean": cat("points_mean"),
                 "nocs_corners": torch.from_numpy(np.stack([t["nocs_corners"] for t in trajs])).float()}
         if all("depth" in t and "mask" in t for t in trajs):
+            _one_image_size([t["depth"].shape for t in trajs], "stack_trajectories")
             meta["pre_fetched"] = {"depth": torch.from_numpy(np.stack([t["depth"][i].astype(np.int32) for t in trajs])),
                                    "mask": torch.from_numpy(np.stack([t["mask"][i] for t in trajs]))}
             if all(k in t for t in trajs for k in DET_KEYS):
                 meta["pre_fetched"].update(pad_detections([{k: t[k][i] for k in DET_KEYS} for t in trajs]))
             if i == 0 and all("coord" in t for t in trajs):
                 meta["pre_fetched"]["coord"] = torch.from_numpy(np.stack([np.asarray(t["coord"], np.uint8) for t in trajs]))
+            if any("camera_K" in t for t in trajs):
+                cams = [(np.asarray(t["camera_K"], np.float64), float(t["camera_depth_unit"])) if "camera_K" in t else _default_camera(default_camera)
+                        for t in trajs]
+                meta["pre_fetched"]["camera"] = {"K": torch.from_numpy(np.stack([c[0] for c in cams])),
+                                                 "depth_unit": torch.tensor([c[1] for c in cams], dtype=torch.float64)}
         if all("ori_paths" in t for t in trajs):
             meta["ori_path"] = [str(t["ori_paths"][i]) for t in trajs]
         frames.append({"points": cat("points"), "labels": cat("labels", torch.int64), "nocs": cat("nocs"), "meta": meta})
     return frames
 
 
-def concat_frame_batches(batches: list) -> list:
+def concat_frame_batches(batches: list, default_camera=None) -> list:
     """[list over T of frame dicts with batch b_k] (equal T, N, P) -> one list over T with batch sum(b_k): the batch
     dimension of every tensor concatenated, path lists chained.  Used by the harness to build a batch out of
     independently generated / loaded trajectories, so that a trajectory's content does not depend on which rank or
-    batch it lands in."""
+    batch it lands in.  Cameras (meta['pre_fetched']['camera']) are carried; where only some batches have one the others' trajectories
+    get `default_camera` or the NOCS REAL camera, as in stack_trajectories."""
     if len(batches) == 1:
         return batches[0]
     T = len(batches[0])
@@ -121,7 +160,16 @@ def concat_frame_batches(batches: list) -> list:
                 "points_mean": torch.cat([f["meta"]["points_mean"] for f in frames]),
                 "nocs_corners": torch.cat([f["meta"]["nocs_corners"] for f in frames])}
         if all("pre_fetched" in f["meta"] for f in frames):
+            _one_image_size([tuple(torch.as_tensor(f["meta"]["pre_fetched"]["depth"]).shape) for f in frames], "concat_frame_batches")
             meta["pre_fetched"] = {k: torch.cat([torch.as_tensor(f["meta"]["pre_fetched"][k]) for f in frames]) for k in ("depth", "mask")}
+            if any("camera" in f["meta"]["pre_fetched"] for f in frames):
+                Ks, units = [], []
+                for f in frames:
+                    cam, b = f["meta"]["pre_fetched"].get("camera"), len(f["meta"]["path"])
+                    K0, u0 = _default_camera(default_camera)
+                    Ks.append(torch.as_tensor(cam["K"]).double().reshape(b, 3, 3) if cam is not None else torch.from_numpy(K0).expand(b, 3, 3))
+                    units.append(torch.as_tensor(cam["depth_unit"]).double().reshape(b) if cam is not None else torch.full((b,), u0, dtype=torch.float64))
+                meta["pre_fetched"]["camera"] = {"K": torch.cat(Ks), "depth_unit": torch.cat(units)}
             if all(k in f["meta"]["pre_fetched"] for f in frames for k in DET_KEYS):
                 meta["pre_fetched"].update(pad_detections([{k: f["meta"]["pre_fetched"][k] for k in DET_KEYS} for f in frames], batched=True))
             if all("coord" in f["meta"]["pre_fetched"] for f in frames):

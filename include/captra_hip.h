@@ -582,6 +582,41 @@ int captra_depth_support_filter(int b, int h, int w, int window, int abs_mm, int
 int captra_image_members(int b, int h, int w, int cap, int border, int negate_z, const int *depth, const unsigned char *mask,
                          const unsigned char *coord, const double *kinv, float *src, float *tgt, int *labels, int *pix, int *counts,
                          captra_stream_t stream);
+/* The CAMERA MODEL of the re-crop and of the first-pose fit (csrc/crop.hip, csrc/image_fit.hip): the five calls above with a camera
+ * PER TRAJECTORY instead of one kmat / kinv for the batch, and the depth unit as data instead of the constant 0.001.  Each takes the
+ * arguments of its plain counterpart with the single matrix replaced by
+ *   ncam            the number of cameras, >= 1;
+ *   cams (ncam,19)  float64 on the device, one row per camera: K row-major (9 doubles, last row 0 0 1), K^-1 row-major (9 doubles),
+ *                   depth_unit (1 double: metres per depth count, finite and > 0; 0.001 for millimetre depth);
+ *   cam_of (b,)     int32 on the device, the camera row of trajectory i.
+ * The pixel and frame convention is the plain calls' (the reference's) everywhere: v = h - row, p_z negated.  The rules:
+ *   - back-projection of trajectory i: ray = Kinv_i (col, h - row, 1); z = double(float(d)); p = (ray * z / ray_z) * unit_i; p_z
+ *     negated -- the plain calls' operations in their order, float64, no contraction, with unit_i where they have 0.001.  With
+ *     unit_i = 0.001 and Kinv_i = kinv: the plain call's outputs, bit for bit.
+ *   - box projection (captra_crop_box_cam, captra_crop_box_det_cam): captra_crop_box's projection with K_i.  Its `* 1000.0` STAYS a
+ *     constant: the projection divides by z, so it is scale-free, and the constant is part of the reference's arithmetic (it decides
+ *     the roundings), not a depth unit.  The 0.05 m radius floor and the detector route's 0.5 m limit stay in metres.
+ *   - cam_of[i] outside [0, ncam) is clamped into the table (memory safety only: the host wrapper builds cam_of, valid by construction).
+ *   - the camera row is uniform per workgroup: its 19 doubles are loaded once per workgroup, not per pixel.
+ * Returns -1 without a launch and without a byte written for ncam < 1 or a NULL cams / cam_of with work to do (b > 0; for
+ * captra_image_members_cam: b, h, w > 0), and for everything the plain counterpart refuses.  The plain entry points keep their
+ * instruction streams: the kernels are templated on a CAM flag whose parameters come last. */
+int captra_crop_box_cam(int b, int h, int w, double radius_factor, const float *trans, const float *scale, int ncam, const double *cams,
+                        const int *cam_of, int *box, double *center, double *radius, captra_stream_t stream);
+int captra_crop_box_det_cam(int b, int h, int w, int ndet, int category, double radius_factor, const float *trans, const float *scale,
+                            int ncam, const double *cams, const int *cam_of, const int *det_boxes, const int *det_class,
+                            const int *det_count, int *box, double *center, double *radius, double *radius_raw, int *sel,
+                            captra_stream_t stream);
+int captra_crop_ball_cam(int b, int h, int w, int cap, const int *depth, const unsigned char *mask, const int *box, const double *center,
+                         const double *radius, int ncam, const double *cams, const int *cam_of, double *pts, unsigned char *obj, int *pix,
+                         int *counts, captra_stream_t stream);
+int captra_crop_ball_det_cam(int b, int h, int w, int cap, int ndet, const int *depth, const unsigned char *mask,
+                             const unsigned char *det_masks, const int *sel, const int *box, const double *center, const double *radius,
+                             int ncam, const double *cams, const int *cam_of, double *pts, unsigned char *obj, int *pix, int *counts,
+                             captra_stream_t stream);
+int captra_image_members_cam(int b, int h, int w, int cap, int border, int negate_z, const int *depth, const unsigned char *mask,
+                             const unsigned char *coord, int ncam, const double *cams, const int *cam_of, float *src, float *tgt,
+                             int *labels, int *pix, int *counts, captra_stream_t stream);
 
 /* Ragged batch of the same operation: the clouds are padded to n_stride points each (xyz (B,n_stride,3)) and cloud i
  * samples m of its FIRST n_per_cloud[i] points (device array of B ints, 1 <= n_per_cloud[i] <= n_stride; NULL = all
