@@ -118,6 +118,7 @@ _SIGNATURES = {
     "captra_part_fit_st_size": [_INT] * 6 + [_F, _P, _P, _P, _INT] + [_P] * 5 + [C.c_ulonglong] + [_P] * 6 + [_INT, _F, _INT, _INT] + [_P] * 16,
     "captra_rot_pool_consensus": [_INT] * 7 + [_F] + [_P] * 4 + [C.c_ulonglong] + [_P] * 6,
     "captra_pose_extrapolate": [_INT, _INT, _INT] + [_P] * 6 + [_F, _F, _F] + [_P] * 7,
+    "captra_part_box_hist": [_INT] * 7 + [_P] * 9 + [_P],
     "captra_seg_softmax_argmax": [_INT, _INT, _INT, _P, _P, _P, _P],
     "captra_copy_multi": [_INT, _P, _P, _P, _P],
     "captra_row_max": [_LL, _INT, _P, _P, _P],
@@ -154,6 +155,7 @@ _AUX_SIGNATURES = {
     "captra_sa1_stream_set_whole": ([_INT], None),
     "captra_neck_chain_set_split": ([_INT], None),
     "captra_image_members_set_split": ([_INT], None),
+    "captra_part_box_set_subhists": ([_INT], None),
     "captra_query_and_group_set_shape": ([_INT, _INT], None),
     "captra_pointwise_mlp_gn_tiles": ([_INT, _INT, _LL], _INT),
     "captra_pointwise_mlp_gn_tiles_ex": ([_INT, _INT, _LL, _P], _INT),

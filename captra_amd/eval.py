@@ -173,6 +173,35 @@ def size_table(name: str, data: dict) -> list:
     return lines
 
 
+def box_table(name: str, data: dict) -> list:
+    """The held box's record of one result pickle (present when the run had track_cfg/box/hold): one line per part with the final
+    half-extents, the first frame after which the box was established (all three extents > 0), the frames that stayed out of the
+    histograms on the guard's verdict (members, but no growth of the held count) and, per axis, the range of the frames' own
+    extents against the range of the held ones (over the frames with members / with an established box)."""
+    frames = [(i, {"extent": np.asarray(r["extent"], np.float64).reshape(-1, 3), "frame": np.asarray(r["frame"], np.float64).reshape(-1, 3),
+                   "added": np.asarray(r["added"]).reshape(-1), "total": np.asarray(r["total"]).reshape(-1)})
+              for i, r in enumerate(data["box"]) if r is not None and "extent" in r]
+    lines = []
+    for p in range(len(frames[0][1]["added"]) if frames else 0):
+        first, skipped, prev_total, own, held = None, 0, 0, [], []
+        for i, r in frames:
+            established = bool((r["extent"][p] > 0).all())
+            if established and first is None:
+                first = i
+            if established:
+                held.append(r["extent"][p])
+            if int(r["added"][p]) > 0:
+                own.append(r["frame"][p])
+                skipped += int(int(r["total"][p]) == prev_total and prev_total < 2 ** 31 - 1)
+            prev_total = int(r["total"][p])
+        span = lambda rows, k: f"{min(x[k] for x in rows):.4f}-{max(x[k] for x in rows):.4f}" if rows else "-"
+        final = " ".join(f"{v:.4f}" for v in frames[-1][1]["extent"][p])
+        axes = "; ".join(f"{a} frame {span(own, k)} held {span(held, k)}" for k, a in enumerate("xyz"))
+        lines.append(f"{name} part {p}: half-extents {final}; established at frame {'-' if first is None else first}; skipped on the guard's "
+                     f"verdict {skipped} (of {len(frames)} frames); {prev_total} values held; {axes}")
+    return lines
+
+
 def otf_thin_table(name: str, data: dict) -> list:
     """The re-crop's on-device thinning record of one result pickle (present when the run had track_cfg/otf_thin/device): one line
     with the frames whose candidate list was thinned, of the frames re-cropped."""
@@ -213,6 +242,7 @@ RECORD_TABLES = (
     ("rot_pool", rot_pool_table, "consensus rotation read-out (track_cfg/rot_pool), per trajectory and part:"),
     ("motion", motion_table, "constant-velocity start pose (track_cfg/motion), per trajectory and part:"),
     ("size", size_table, "held size (track_cfg/size), frames per trajectory and part:"),
+    ("box", box_table, "held box (track_cfg/box), per trajectory and part:"),
     ("otf_thin", otf_thin_table, "re-crop lists thinned on the device (track_cfg/otf_thin), frames per trajectory:"),
     ("depth_filter", depth_filter_table, "flying depth pixels removed at upload (track_cfg/depth_filter), per trajectory:"),
     ("image_fit", image_fit_table, "first pose fitted from frame 0's images (init_frame/image_fit), per trajectory:"),

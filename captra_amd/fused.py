@@ -279,10 +279,14 @@ def pointwise_mlp(x, lin: PackedLinear, act: int = ACT_RELU, out=None):
     return out
 
 
+MLP2_SPAN_LIMIT = 1 << 30          # bytes one buffer descriptor of captra_pointwise_mlp2 spans: both sources lie inside it
+
+
 def pointwise_mlp2(x, x2, lin: PackedLinear, act: int = ACT_RELU):
     """act(W [x; x2] + b) without building the concat (captra_pointwise_mlp2): x (B,c,l), x2 (B,c2,l) or (B,c2,1) (one vector per
     cloud, read for every position); exact fp32, bit-identical to pointwise_mlp on the concatenated tensor.  None when the shape is
-    outside the kernel's range or the tensors lie too far apart for one buffer descriptor: the caller concatenates."""
+    outside the kernel's range: the caller concatenates.  Two tensors that lie too far apart for one buffer descriptor -- where the
+    allocator put them is no property of the call -- are copied into one buffer first: the same launch, the same bits."""
     if not exact_path() or lin.cout <= 64 or x.dim() != 3 or x2.dim() != 3:
         return None
     L.require_device(x, x2)
@@ -290,8 +294,12 @@ def pointwise_mlp2(x, x2, lin: PackedLinear, act: int = ACT_RELU):
     bcast = x2.shape[2] == 1 and l != 1
     assert lin.cin == c + x2.shape[1] and (bcast or x2.shape[2] == l), (x.shape, x2.shape, lin.cin)
     span = 4 * (x.numel() + x2.numel())
-    if abs(x2.data_ptr() - x.data_ptr()) + span >= (1 << 30):
-        return None
+    if abs(x2.data_ptr() - x.data_ptr()) + span >= MLP2_SPAN_LIMIT:
+        if span + 256 >= (1 << 30):
+            return None
+        at = (x.numel() + 63) // 64 * 64                    # (x2 keeps a 256-byte aligned start)
+        both = torch.empty(at + x2.numel(), dtype=torch.float32, device=x.device)
+        x, x2 = both[:x.numel()].view(x.shape).copy_(x), both[at:].view(x2.shape).copy_(x2)
     out = torch.empty(B, lin.cout, l, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         L.call("captra_pointwise_mlp2", B, lin.cin, c, lin.cout, l, L.ptr(x), L.ptr(x2), 1 if bcast else 0, L.ptr(lin.wt), L.ptr(lin.bias), act, L.ptr(out))

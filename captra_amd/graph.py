@@ -200,8 +200,8 @@ class TrackStepGraph:
             pairs.append((labels, self.labels))
         # the step's inputs into the captured buffers: one launch when they are plain device tensors of the captured types
         if all(a.is_cuda and a.is_contiguous() and a.dtype == b.dtype and a.shape == b.shape and a.element_size() % 4 == 0 for a, b in pairs):
-            # (points, mean, the pose dict -- 3 keys, 6 with the motion model, 9 with the size state too -- and labels: at most 12 jobs,
-            # within the launch's 16)
+            # (points, mean, the pose dict -- 3 keys, 6 with the motion model, 9 with the size state too, 10 with the box histograms --
+            # and labels: at most 13 jobs, within the launch's 16)
             assert len(pairs) <= 16, len(pairs)
             fused.copy_multi(pairs)
         else:
@@ -235,7 +235,8 @@ class TrackLanes:
         if lanes < 1 or B % lanes:
             raise ValueError(f"{B} trajectories do not split into {lanes} lanes")
         # (the options whose state travels in the pose dict: what track_options.entering reads of a model)
-        self._options = types.SimpleNamespace(motion=getattr(model, "motion", None), size=getattr(model, "size", None))
+        self._options = types.SimpleNamespace(motion=getattr(model, "motion", None), size=getattr(model, "size", None),
+                                              box=getattr(model, "box", None))
         pose = self._entering(pose)
         dev = points.device
         per = B // lanes
@@ -294,7 +295,7 @@ class TrackLanes:
                     pairs += [(g.npcs_pred[k], dst[s]) for k, dst in self.npcs_ring[slot].items()]
                 # (6 pose + 3 map jobs, 4 more with a guard record, 2 with the robust fit's: 15, within the launch's 16; the consensus
                 # read-out's 2 on top of all of them take a second launch, and so do the motion model's 6 pose + 5 record jobs and the
-                # size state's 6 pose + 4 record jobs)
+                # size state's 6 pose + 4 record jobs and the box histograms' 2 pose + 4 record jobs)
                 for j in range(0, len(pairs), 16):
                     fused.copy_multi(pairs[j:j + 16])
                 self.written[slot][l].record(st)

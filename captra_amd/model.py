@@ -130,6 +130,7 @@ class EvalTrackModel(BaseModel):
         self.rot_pool = self.net.rot_pool = O.rot_pool_cfg(cfg)            # every step's rotation from the votes' consensus
         self.motion = O.motion_cfg(cfg)                                    # every step starts from a constant-velocity prediction
         self.size = self.net.size = O.size_cfg(cfg)                        # every step holds the part's running scale
+        self.box = O.box_cfg(cfg)                                          # every step holds the part's box (NOCS extents)
         self.nocs_otf = bool(cfg.get("nocs_otf", False))
         self.otf_thin = O.otf_thin_cfg(cfg)                                # the re-crop's over-long lists thinned on the device
         self._otf_thin_rec = {}             # frame -> {first trajectory of a slice: its thinned flags (b,) int32 on the device}
@@ -485,9 +486,27 @@ class EvalTrackModel(BaseModel):
         size_state = {k: pose[k] for k in O.SIZE_KEYS} if self.size is not None else None
         if self.guard is not None:
             pose = self._guard_step(input, npcs_pred, pose)
+        # track_cfg/box: behind the guard (its verdict decides whether the frame counts), beside the motion model: neither reads the other
+        box_hist = self._box_step(input, npcs_pred, entered) if self.box is not None else None
         if self.motion is not None:
             pose = self._motion_step(npcs_pred, entered, pose)
-        return pose if size_state is None else {**{k: v for k, v in pose.items() if k not in size_state}, **size_state}
+        if size_state is not None:
+            pose = {**{k: v for k, v in pose.items() if k not in size_state}, **size_state}
+        return pose if box_hist is None else {**{k: v for k, v in pose.items() if k != O.BOX_KEY}, O.BOX_KEY: box_hist}
+
+    def _box_step(self, input, npcs_pred, entered):
+        """The held box behind the guard, on the labels the fit used and the per-part NOCS maps: the frame's coordinates into the
+        histograms that entered the step (`entered`: box_hist); its record joins CoordinateNet's maps (`box_*`); -> the new histograms."""
+        from .pose_utils.pose_fit import part_box_hist
+        x = self.box
+        labels = input.get("pred_labels_i32")
+        if labels is None:
+            labels = input["pred_labels"].int().contiguous()
+        verdict = npcs_pred["guard_verdict"] if self.guard is not None else None
+        new, info = part_box_hist(labels, input["pred_nocs"].float().contiguous(), entered[O.BOX_KEY], bins=x["bins"], radial=x["radial"],
+                                  quantile_permille=x["quantile_permille"], min_points=x["min_points"], verdict=verdict)
+        O.put_record(npcs_pred, "box", info)
+        return new
 
     def _motion_step(self, npcs_pred, entered, pose):
         """The motion model behind the fit and the guard: the pose the NEXT step starts from, out of the result that entered this
@@ -912,6 +931,11 @@ class EvalTrackModel(BaseModel):
             # every frame in one launch and one read; float64 at the pickle boundary like the host function (same values, bit for bit)
             corners = pred_nocs_corners_device(torch.stack([m[0] for m in maps]), torch.stack([m[1] for m in maps]), self.num_parts)
             corner_list.extend(corners.double().cpu().numpy())
+        if "box" in self.pred_dict:
+            # track_cfg/box: the box held after frame i (causal) where it is established, the frame's own otherwise
+            from .pose_utils.bbox_utils import held_box_corners
+            for i in range(1, len(corner_list)):
+                corner_list[i] = held_box_corners(corner_list[i], self.pred_dict["box"][i]["extent"].detach().cpu().numpy())
         to_np = lambda pose: {k: v.detach().cpu().numpy() for k, v in pose.items()}
         save_dict = {"pred": {"poses": [to_np(p) for p in self.pred_dict["poses"]], "corners": corner_list},
                      "gt": {"poses": [to_np(f["gt_part"]) for f in self.feed_dict], "corners": gt_corners},
@@ -934,7 +958,7 @@ class EvalTrackModel(BaseModel):
         reference, or with cfg['eval_device'] all frames in one call on the GPU: `_device_iou`).  Keys as in the reference, including its quirk of storing the per-frame NOCS losses under
         'frame_seg'."""
         from .loss import choose_coord_by_label, compute_miou_loss, compute_nocs_loss
-        from .pose_utils.bbox_utils import eval_single_part_iou, get_pred_nocs_corners
+        from .pose_utils.bbox_utils import eval_single_part_iou, get_pred_nocs_corners, held_box_corners
         avg_pred, avg_init, all_pred, all_init = {}, {}, {}, {}
         avg_iou, all_iou, seg_losses, all_seg, nocs_losses, all_nocs = {}, {}, [], {}, [], {}
         poses = self.pred_dict["poses"]
@@ -967,6 +991,8 @@ class EvalTrackModel(BaseModel):
             elif eval_iou:
                 pred_nocs = choose_coord_by_label(npcs_pred["nocs"].transpose(-1, -2), pred_labels)                 # (B,N,3)
                 pred_corners = torch.from_numpy(get_pred_nocs_corners(pred_labels, pred_nocs, self.num_parts)).float()
+                if "box" in self.pred_dict:         # track_cfg/box: the held box where it is established
+                    pred_corners = held_box_corners(pred_corners, self.pred_dict["box"][i]["extent"].cpu())
                 iou, per_iou = eval_single_part_iou(gt_corners, pred_corners, self.feed_dict[i]["gt_part"], pose,
                                                     separate="both", nocs=self.nocs_otf, sym=self.sym)
                 iou = {name: {p: float(v) for p, v in d.items()} for name, d in iou.items()}
@@ -994,6 +1020,9 @@ class EvalTrackModel(BaseModel):
         from .pose_utils.bbox_utils import eval_single_part_iou_device, pred_nocs_corners_device
         names, idx = ("npcs_iou", "iou", "gt_bbox_iou"), [f[0] for f in frames]
         pred_corners = pred_nocs_corners_device(torch.stack([f[1] for f in frames]), torch.stack([f[2] for f in frames]), self.num_parts)
+        if "box" in self.pred_dict:             # track_cfg/box: the held box where it is established
+            from .pose_utils.bbox_utils import held_box_corners
+            pred_corners = held_box_corners(pred_corners, torch.stack([self.pred_dict["box"][i]["extent"] for i in idx]))
         dev = pred_corners.device
         stack = lambda ds: {k: torch.stack([d[k].to(dev) for d in ds]) for k in ("rotation", "translation", "scale")}
         res = eval_single_part_iou_device(gt_corners.to(dev), pred_corners, stack([self.feed_dict[i]["gt_part"] for i in idx]),

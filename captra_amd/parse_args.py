@@ -60,6 +60,11 @@ _FLAGS = [  # (name, type, default)
     ("track_cfg/size/hold", boolean_string, argparse.SUPPRESS), ("track_cfg/size/max_ratio", float, argparse.SUPPRESS),
     ("track_cfg/size/min_frames", int, argparse.SUPPRESS), ("track_cfg/size/max_frames", int, argparse.SUPPRESS),
     ("track_cfg/size/reset_after", int, argparse.SUPPRESS), ("track_cfg/size/init_frames", int, argparse.SUPPRESS),
+    # every step holds the part's box: a histogram of the predicted NOCS coordinates over the track (track_options.py: box_cfg); off
+    # unless hold is True, and then quantile is required.  Not given = not in the namespace at all, like the size flags
+    ("track_cfg/box/hold", boolean_string, argparse.SUPPRESS), ("track_cfg/box/quantile", float, argparse.SUPPRESS),
+    ("track_cfg/box/bins", int, argparse.SUPPRESS), ("track_cfg/box/min_points", int, argparse.SUPPRESS),
+    ("track_cfg/box/radial", boolean_string, argparse.SUPPRESS),
     # optimisation
     ("total_epoch", int, None), ("optimizer", str, None), ("weight_decay", float, None), ("learning_rate", float, None),
     ("lr_policy", str, None), ("lr_gamma", float, None), ("lr_step_size", int, None), ("lr_clip", float, None), ("freq/save", int, None),

@@ -143,6 +143,18 @@ def get_pred_nocs_corners(pred_seg, nocs_pred, num_parts: int) -> np.ndarray:
     return out
 
 
+def held_box_corners(corners, extent):
+    """track_cfg/box: the reference's corners (...,P,2,3) and the held half-extents (...,P,3) -> corners (...,P,2,3): [-e, +e] where
+    all three extents of a part are > 0 (its box is established), else the reference's corners of that frame and part.  numpy in,
+    numpy out (the corners' dtype); torch in, torch out (on the corners' device, in the corners' dtype)."""
+    if hasattr(corners, "detach"):
+        import torch
+        e = extent.to(device=corners.device, dtype=corners.dtype)
+        return torch.where((e > 0).all(-1)[..., None, None], torch.stack([-e, e], dim=-2), corners)
+    corners, e = np.asarray(corners), np.asarray(extent).astype(np.asarray(corners).dtype)
+    return np.where((e > 0).all(-1)[..., None, None], np.stack([-e, e], axis=-2), corners)
+
+
 def calc_part_iou_list(gt_bbox_list, pred_bbox, separate="both", nocs=False):
     """Best IoU of every predicted part box against the candidate ground-truth boxes: boxes (B,P,8,3) ->
     ({part: batch mean}, {part: (B,) values}); separate=True / False picks one of the two like the reference."""

@@ -292,3 +292,34 @@ def pose_extrapolate(rot0, trans0, rot1, trans1, measured0, sym: bool, max_angle
                L.ptr(verdict), float(gain), float(max_angle), float(max_shift), L.ptr(rot_next), L.ptr(trans_next), L.ptr(measured1),
                L.ptr(used), L.ptr(angle), L.ptr(shift))
     return rot_next, trans_next.unsqueeze(-1), measured1, {"used": used, "angle": angle, "shift": shift}
+
+
+BOX_BINS = (64, 128, 256, 512)      # the histogram widths captra_part_box_hist takes
+
+
+def part_box_hist(labels_i32, src_cn, state, *, bins, radial, quantile_permille, min_points, verdict=None):
+    """Holding the track's box in one launch (captra_part_box_hist, include/captra_hip.h): labels (B,N) int32 = the labels the fit used,
+    src_cn (B,P,3,N) predicted NOCS, state = the histograms (B,P,3,bins) int32 that entered the frame or None (a track's start: empty),
+    verdict (B,P) int32 = the guard's codes of this frame (GUARD_VERDICTS) or None (every frame counts); radial: a symmetric category's
+    x and z extents from the radius sqrt(x^2 + z^2).
+    -> (new state (B,P,3,bins) int32 -- a new tensor, `state` is not written --,
+        info {'extent' (B,P,3) float32: the held half-extents after this frame, 0 where fewer than min_points values are held,
+              'frame' (B,P,3) float32: this frame's own, 'added' (B,P) int32: the frame's members, 'total' (B,P) int32: values held})."""
+    B, P, _, N = src_cn.shape
+    dev = src_cn.device
+    bins = int(bins)
+    if state is not None:
+        state = state.contiguous()
+        assert state.dtype == torch.int32 and tuple(state.shape) == (B, P, 3, bins), (state.dtype, tuple(state.shape))
+    if verdict is not None:
+        verdict = verdict.int().contiguous()
+    L.require_device(labels_i32, src_cn, state, verdict)
+    new_state = torch.empty(B, P, 3, bins, dtype=torch.int32, device=dev)
+    extent = torch.empty(B, P, 3, dtype=torch.float32, device=dev)
+    frame = torch.empty(B, P, 3, dtype=torch.float32, device=dev)
+    added = torch.empty(B, P, dtype=torch.int32, device=dev)
+    total = torch.empty(B, P, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("captra_part_box_hist", B, P, N, bins, 1 if radial else 0, int(quantile_permille), int(min_points), L.ptr(labels_i32),
+               L.ptr(src_cn), L.ptr(verdict), L.ptr(state), L.ptr(new_state), L.ptr(extent), L.ptr(frame), L.ptr(added), L.ptr(total))
+    return new_state, {"extent": extent, "frame": frame, "added": added, "total": total}

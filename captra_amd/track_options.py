@@ -283,11 +283,59 @@ def size_cfg(cfg):
     return out
 
 
+def box_cfg(cfg):
+    """track_cfg: {box: {hold: True, quantile: <q>, bins: 128, min_points: 16, radial: False}}: every step adds the frame's predicted NOCS
+    coordinates to a per-part histogram of |x|, |y|, |z| kept over the track -- a part's box is a constant of the instance -- and reads
+    the box's half-extents out of it as the `quantile` of each axis, rounded up to the bin's edge (csrc/pose_box.hip,
+    include/captra_hip.h: captra_part_box_hist -- one launch behind the guard, captured with the step); a frame the guard found lost or
+    too thin stays out.  The histograms travel in the pose dict (box_hist) and the frame's read-out is recorded (pred_dict / pickle
+    'box'); where a part's box is established it replaces the per-frame maximum in pred['corners'] and in the box IoUs.  None when
+    absent or hold is not set; quantile has no default -- it depends on the trained network's outlier rate --, lies in [0.5, 1] and is
+    a whole number of thousandths; radial: the x and z extents of a symmetric category from the radius sqrt(x^2 + z^2), which does
+    not depend on the arbitrary in-plane angle (an error on any other category).
+    -> {'quantile_permille', 'bins', 'min_points', 'radial'}."""
+    s = cfg["track_cfg"].get("box")
+    if s is None or not s.get("hold", False):
+        return None
+    q = s.get("quantile")
+    if q is None:
+        raise ValueError("track_cfg/box/hold needs track_cfg/box/quantile (the share of a part's points inside the box per axis, in "
+                         "[0.5, 1]): it has no default")
+    if isinstance(q, bool) or not isinstance(q, (int, float, np.integer, np.floating)) or not np.isfinite(q) or not 0.5 <= float(q) <= 1.0:
+        raise ValueError(f"track_cfg/box/quantile must be a number in [0.5, 1], got {q!r}")
+    permille = int(round(float(q) * 1000.0))
+    if abs(float(q) * 1000.0 - permille) > 1e-6:
+        raise ValueError(f"track_cfg/box/quantile must be a whole number of thousandths (the kernel's quantile is an integer per mille), got {q!r}")
+    from .pose_utils.pose_fit import BOX_BINS
+    bins, min_points = s.get("bins"), s.get("min_points")
+    bins, min_points = 128 if bins is None else bins, 16 if min_points is None else min_points
+    if isinstance(bins, bool) or int(bins) != bins or int(bins) not in BOX_BINS:
+        raise ValueError(f"track_cfg/box/bins must be one of {BOX_BINS}, got {s.get('bins')!r}")
+    if isinstance(min_points, bool) or int(min_points) != min_points or not 1 <= int(min_points) < 2 ** 31:
+        raise ValueError(f"track_cfg/box/min_points must be an integer >= 1, got {s.get('min_points')!r}")
+    radial = bool(s.get("radial", False))
+    if radial and not cfg["obj_sym"]:
+        raise ValueError(f"track_cfg/box/radial: the radial extent is for symmetric categories (obj_sym), category "
+                         f"{cfg['obj_category']} is not one: its in-plane angle is part of the pose")
+    return {"quantile_permille": permille, "bins": int(bins), "min_points": int(min_points), "radial": radial}
+
+
 # The pose dict that travels from frame to frame: these three, with track_cfg/motion three more -- the pose the next step starts
-# from and whether the dict's own pose is a measured result (a track's start is not) -- and with track_cfg/size the three words of
-# the size state.  The dict is the loop's whole state.
+# from and whether the dict's own pose is a measured result (a track's start is not) --, with track_cfg/size the three words of
+# the size state and with track_cfg/box the box histograms.  The dict is the loop's whole state.
 POSE_KEYS = ("rotation", "scale", "translation")
 SIZE_KEYS = ("size_mean", "size_n", "size_miss")
+BOX_KEY = "box_hist"
+
+
+def entering_box(pose, box):
+    """track_cfg/box: a dict without the histograms is a track's START -- empty ones, (B,P,3,bins) int32 zeros.  A dict that carries
+    them passes through."""
+    if BOX_KEY in pose:
+        return pose
+    import torch
+    scale = pose["scale"]
+    return {**pose, BOX_KEY: torch.zeros(tuple(scale.shape) + (3, box["bins"]), dtype=torch.int32, device=scale.device)}
 
 
 def entering_size(pose, size):
@@ -315,11 +363,13 @@ def entering_pose(pose):
 
 
 def entering(pose, model):
-    """The travelling dict of `model`'s options (its `motion` / `size` attributes; absent or None: off) for a pose entering a step."""
+    """The travelling dict of `model`'s options (its `motion` / `size` / `box` attributes; absent or None: off) for a pose entering a step."""
     if getattr(model, "motion", None) is not None:
         pose = entering_pose(pose)
     if getattr(model, "size", None) is not None:
         pose = entering_size(pose, model.size)
+    if getattr(model, "box", None) is not None:
+        pose = entering_box(pose, model.box)
     return pose
 
 
@@ -328,7 +378,8 @@ def start_pose(pose):
     if "next_rotation" not in pose:
         return pose
     start = {"rotation": pose["next_rotation"], "scale": pose["scale"], "translation": pose["next_translation"]}
-    start.update((k, pose[k]) for k in SIZE_KEYS if k in pose)      # (track_cfg/size: the state stays with the pose it belongs to)
+    # (track_cfg/size, track_cfg/box: the state stays with the pose it belongs to)
+    start.update((k, pose[k]) for k in SIZE_KEYS + (BOX_KEY,) if k in pose)
     return start
 
 
@@ -340,7 +391,10 @@ STEP_RECORDS = {"guard": ("guard_", ("count", "inliers", "rms", "verdict")),    
                 # used int32, angle (degrees) / shift float32, and the predicted pose itself: (B,P,3,3), (B,P,3,1)
                 "motion": ("motion_", ("used", "angle", "shift", "rotation", "translation")),
                 # held / accepted int32, free = the frame's own scale float32, n = the frames in the mean after this one int32
-                "size": ("size_", ("held", "accepted", "free", "n"))}
+                "size": ("size_", ("held", "accepted", "free", "n")),
+                # extent = the held half-extents after the frame (0: not established), frame = the frame's own: (B,P,3) float32;
+                # added = the frame's members, total = the values held per axis: int32
+                "box": ("box_", ("extent", "frame", "added", "total"))}
 # The host loop's records, ONE (B,) int32 tensor per frame (None: a frame without) -> the key that wraps it in the pickle.
 # otf_thin: which trajectories' lists were thinned (its sum: the frame's thinned instances); depth_filter: the pixels set to 0
 LOOP_RECORDS = {"otf_thin": "thinned", "depth_filter": "removed"}
@@ -362,8 +416,9 @@ def commit_with_records(commit, records):
         for name, frames in records.items():
             prefix, keys = STEP_RECORDS[name]
             frames[i] = {k: npcs.pop(prefix + k) for k in keys}
-        if "motion" in records or "size" in records:
-            # a committed frame keeps the three keys; the prediction is in its record, the size state only in the travelling dict
+        if "motion" in records or "size" in records or "box" in records:
+            # a committed frame keeps the three keys; the prediction is in its record, the size state and the box histograms only
+            # in the travelling dict
             pose = {k: pose[k] for k in POSE_KEYS}
         return npcs, pose
     return wrapped if records else commit

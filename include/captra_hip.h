@@ -1052,6 +1052,31 @@ int captra_pose_extrapolate(int b, int p, int sym, const float *rot0, const floa
                             float *rot_next, float *trans_next, int *measured1, int *used, float *angle, float *shift,
                             captra_stream_t stream);
 
+/* Holding a track's box (no reference counterpart: get_pred_nocs_corners / captra_part_extent take the largest |x|, |y|, |z| of every
+ * frame by itself, so one wild NOCS prediction sets the box): per (trajectory, part) a histogram of the per-axis values over [0, 1),
+ * accumulated from frame to frame, and a quantile read out of it.  One launch, one workgroup of 256 threads per (b, q), LDS integer
+ * atomics; every step is integer arithmetic or an exact fp32 operation, so no output depends on the order of the points.
+ *   labels (B,N) i32, src (B,P,3,N) f32: the labels the fit used and the per-part NOCS maps (the layout captra_part_fit_guard reads).
+ *   member  : point i of (b, q) with labels[b,i] == q and src[b,q,:,i] all finite; a label outside [0, P) belongs to no part.
+ *   value   : a_k = |src[b,q,k,i]|; radial != 0 (a symmetric category, whose in-plane angle is arbitrary): a_1 = |y| and
+ *             a_0 = a_2 = r = sqrt(x x + z z), each operation rounded to fp32 once, none contracted.
+ *   bin     : bins - 1 when a >= 1 or a is not finite (an overflowed r), else (int)(a * bins); bins in {64, 128, 256, 512}.
+ *   F       : the frame's histogram (3,bins) of the members; added (B,P) i32 = their number.
+ *   state   : hist_out (B,P,3,bins) i32 = min(max(hist_in, 0) + F, 2^31 - 1), summed in 64 bits, where verdict (B,P) i32 -- the codes
+ *             of captra_part_fit_guard for THIS frame -- is NULL, 0 (ok) or 3 (recovered); with 1 (too_few) or 2 (lost), or any other
+ *             code, F stays out: hist_out = min(max(hist_in, 0), 2^31 - 1).  hist_in NULL = an empty state (zeros); hist_out may be
+ *             the same pointer as hist_in.
+ *   read-out: per axis k of a histogram H: T = the sum of H[k][:] in 64 bits; T < min_points -> 0.0f (not established); else
+ *             need = (T * quantile_permille + 999) / 1000 in 64-bit integers, j* = the smallest bin whose cumulative count reaches
+ *             need, and the value is (j* + 1) / bins: the bin's UPPER edge (an extent that errs outward by less than one bin), exact.
+ *             extent (B,P,3) f32 reads hist_out, frame_extent (B,P,3) f32 reads F; total (B,P) i32 = axis 0's T of hist_out, clamped
+ *             to 2^31 - 1.
+ * b, p, n < 1, p > 8, 1536 B P beyond INT_MAX, bins not one of the four, quantile_permille outside [500, 1000], min_points < 1, or a
+ * NULL among labels, src, hist_out, extent, frame_extent, added, total return -1 without a launch. */
+int captra_part_box_hist(int b, int p, int n, int bins, int radial, int quantile_permille, int min_points, const int *labels,
+                         const float *src, const int *verdict, const int *hist_in, int *hist_out, float *extent, float *frame_extent,
+                         int *added, int *total, captra_stream_t stream);
+
 /* Batched 3x3 orthogonal Procrustes: R = U diag(1,1,det(U V^T)) V^T with U S V^T = tgt^T src
  * (rotate_pts_batch procrustes.py:25-56).  src, tgt (nb,N,3) -> rot (nb,3,3).  One-sided Jacobi. */
 int captra_procrustes_rot3(int nb, int n, const float *src, const float *tgt, float *rot,
@@ -1129,6 +1154,7 @@ void captra_sa1_stream_set_whole(int windows); /* level-1 stream kernel: bits 0-
 void captra_sa_bf16_set_variant(int v);     /* bf16 SA scales: bit 0 = small-input scales without gather prefetch / fragment ring, bit 3 = SA2 scales on
                                                sa_bf16_kernel; bits 4.. (ablations with WRONG results, timing only) exist in -DCAPTRA_ABLATIONS=1 builds only */
 void captra_image_members_set_split(int n); /* captra_image_members: workgroups per image (0 = default: as many as fill the device twice, shares of >= 4096 pixels) */
+void captra_part_box_set_subhists(int sub); /* captra_part_box_hist: LDS histograms per workgroup, 1 = one all waves add into, 4 = one per wave (0 = default; same results) */
 void captra_neck_chain_set_split(int n); /* captra_neck_chain_bf16, three-layer modules: workgroups sharing the last layer of a position tile (1 / 2 / 4, default 4) */
 void captra_query_and_group_set_shape(int mcb, int cc); /* captra_query_and_group: centres per workgroup, channels per chunk (0 = heuristic) */
 void captra_group_set_shape(int lds_kb, int ccmax, int ppb); /* group_points: staging budget (KiB, <= 64), channels per workgroup, positions per
